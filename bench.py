@@ -7,6 +7,12 @@ clique).
 
     python bench.py --gpus N --steps K --warmup W
     (N>1 launched by the driver via torch.distributed.run, one rank/GPU)
+
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+``--dump-outputs DIR`` additionally writes what the last timed step
+returned (loss, grad norm, a seeded sample of the updated weights) as
+``DIR/<name>.npy``. ``--full`` is reserved for
+measurements beyond the headline figure; there are none today.
 """
 
 from __future__ import annotations
@@ -54,7 +60,18 @@ def main():
         "steady state; measured ~3%% slower than eager on MI355X r01 — "
         "launch gaps are already hidden — so default off)",
     )
+    ap.add_argument(
+        "--dump-outputs", metavar="DIR", default=None,
+        help="after the timed steps, write the last step's outputs "
+        "(loss, grad norm, a seeded sample of the weights) to DIR/*.npy",
+    )
+    ap.add_argument(
+        "--full", action="store_true",
+        help="also run the measurements beyond the headline figure "
+        "(none today: the plain run is the whole benchmark)",
+    )
     args = ap.parse_args()
+    assert args.steps >= 1, "--steps must be at least 1"
 
     n = args.gpus
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -100,7 +117,15 @@ def main():
     }
 
     module = LlamaModule(cfg)
-    module.setup()
+    if use_gpu:
+        # random-init the 8B weights on the device: filling them on the
+        # host and copying them over took ~30 s of every run. Each weight
+        # is still seeded individually, so runs stay identical.
+        with torch.device("cuda"):
+            module.setup()
+        torch.cuda.empty_cache()
+    else:
+        module.setup()
     module.configure_optimizers(max_steps=args.steps + args.warmup)
 
     vocab = cfg["model"]["vocab_size"]
@@ -151,14 +176,16 @@ def main():
                 sid.copy_(mb["input_ids"], non_blocking=True)
                 slab.copy_(mb["labels"], non_blocking=True)
                 g.replay()
-            module.optimizer.step()
+            gnorm = module.optimizer.step()
             module.scheduler.step()
-            return
+            return sloss, gnorm
         module.optimizer.zero_grad()
-        module.forward_backward_step(iter(micros))
-        module.optimizer.step()
+        loss = module.forward_backward_step(iter(micros))
+        gnorm = module.optimizer.step()
         module.scheduler.step()
+        return loss, gnorm
 
+    last = None
     for _ in range(args.warmup):
         one_step()
 
@@ -168,7 +195,7 @@ def main():
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     if use_gpu:
         torch.cuda.synchronize()
     if world > 1:
@@ -208,8 +235,36 @@ def main():
             ),
             flush=True,
         )
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, module, *last)
     if world > 1:
         dist.destroy_process_group()
+
+
+_SAMPLE_PER_TENSOR = 8192
+
+
+def _dump_outputs(out_dir, module, loss, gnorm):
+    """Write what the last timed step handed back: its loss, its global
+    grad norm, and the weights it left behind. The weights are a fixed,
+    seeded sample (<= 8192 elements per parameter, in named_parameters
+    order; rank 0's shard at TP>1), ~6 MB for the 8B model."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"),
+            loss.detach().double().cpu().numpy())
+    np.save(os.path.join(out_dir, "grad_norm.npy"),
+            gnorm.detach().double().cpu().numpy())
+    gen = torch.Generator().manual_seed(20240531)
+    parts = []
+    for _, p in module.model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > _SAMPLE_PER_TENSOR:
+            idx = torch.randint(0, flat.numel(), (_SAMPLE_PER_TENSOR,), generator=gen)
+            flat = flat[idx.to(flat.device)]
+        parts.append(flat.float().cpu())
+    np.save(os.path.join(out_dir, "weights_sample.npy"), torch.cat(parts).numpy())
 
 
 if __name__ == "__main__":
