@@ -39,6 +39,7 @@ from ..parallel.mappings import (
     scatter_to_sequence_parallel_region,
 )
 from ..ops import flash_attn_func, swiglu
+from ..ops.flash_attn import mask_to_kv_range_tensors
 from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
 from ..ops.rmsnorm import RMSNorm
 
@@ -64,6 +65,12 @@ class LlamaConfig:
     kv_replicator: int = 1
     fuse_qkv: bool = True
     activation_checkpoint: Optional[str] = None  # None | "selective" | "full"
+    # attention for batches whose attention_mask has zeros: "eager" = SDPA
+    # with an additive mask; "flash" = flash kernel with a per-row key
+    # range (fp32 reference on CPU); "auto" = "flash" on GPU in bf16 with
+    # head_dim 64/128, else "eager". A mask with holes inside a row always
+    # runs "eager".
+    padded_attention: str = "auto"
     dtype: str = "float32"
 
     @property
@@ -203,12 +210,16 @@ class LlamaAttention(nn.Module):
             k, v = kv.chunk(2, dim=-1)
         return q, k, v
 
-    def core_attention(self, q, k, v):
+    def core_attention(self, q, k, v, kv_range=None):
         """q/k/v: [b, h, s, d] bf16 → o [b, h, s, d]. The recompute unit for
         selective activation checkpointing (reference CoreAttention).
         Under context parallelism the flash kernel runs inside the CP ring
-        (reference ring-attention dispatch, modeling_llama.py:482-489)."""
+        (reference ring-attention dispatch, modeling_llama.py:482-489).
+        kv_range: (kv_lo, kv_hi) int32 [b] visible key range of a padded
+        batch (LlamaModel.forward), None for dense batches."""
         if ps.get_context_model_parallel_world_size() > 1:
+            assert kv_range is None, \
+                "padding masks are not supported under context parallelism"
             from ..ops.ring_attn import ring_flash_attn
 
             # the ring path has no sliding-window support yet: windowed
@@ -223,10 +234,11 @@ class LlamaAttention(nn.Module):
         return flash_attn_func(
             q, k, v, causal=True, scale=self.scale,
             window=getattr(self.cfg, "sliding_window", None),
+            kv_range=kv_range,
         )
 
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
-                layer_idx: int = 0, pad_mask=None):
+                layer_idx: int = 0, pad_mask=None, kv_range=None):
         # x: [s(, /tp if SP), b, h]
         s_dim, b = x.size(0), x.size(1)
         d = self.head_dim
@@ -262,9 +274,10 @@ class LlamaAttention(nn.Module):
                 window=getattr(self.cfg, "sliding_window", None),
             )
         elif self.cfg.activation_checkpoint == "selective" and self.training:
-            o = _ckpt(self.core_attention, q, k, v, use_reentrant=False)
+            o = _ckpt(self.core_attention, q, k, v, kv_range,
+                      use_reentrant=False)
         else:
-            o = self.core_attention(q, k, v)
+            o = self.core_attention(q, k, v, kv_range)
         o = o.permute(2, 0, 1, 3).reshape(s_full, b, self.n_heads_local * d)
         return self.o_proj(o)
 
@@ -298,10 +311,10 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp = LlamaMLP(cfg, layer_idx)
 
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
-                layer_idx: int = 0, pad_mask=None):
+                layer_idx: int = 0, pad_mask=None, kv_range=None):
         x = x + self.self_attn(self.input_layernorm(x), cos, sin, pos_offset,
                                cache=cache, layer_idx=layer_idx,
-                               pad_mask=pad_mask)
+                               pad_mask=pad_mask, kv_range=kv_range)
         x = x + self.mlp(self.post_attention_layernorm(x))
         return x
 
@@ -331,6 +344,39 @@ class LlamaModel(nn.Module):
 
             tag_sequence_parallel_params(self)
 
+    def _padding(self, attention_mask, kv_cache):
+        """Decide once per forward how a padded batch is attended: returns
+        (pad_mask, kv_range), at most one of them set. pad_mask ([b, s]
+        bool, True at pad keys) selects the eager SDPA branch; kv_range
+        (int32 kv_lo, kv_hi [b]) the ranged flash kernel. One host sync."""
+        if attention_mask is None:
+            return None, None
+        mode = self.cfg.padded_attention
+        assert mode in ("auto", "flash", "eager"), \
+            f"padded_attention must be auto|flash|eager, got {mode!r}"
+        flash = kv_cache is None and (
+            mode == "flash"
+            or (mode == "auto" and attention_mask.is_cuda
+                and self.cfg.torch_dtype == torch.bfloat16
+                and self.cfg.head_dim in (64, 128))
+        )
+        if not flash:
+            if not bool((attention_mask == 0).any()):
+                return None, None
+            assert ps.get_context_model_parallel_world_size() == 1, \
+                "padding masks are not supported under context parallelism"
+            return attention_mask == 0, None
+        lo, hi, contiguous = mask_to_kv_range_tensors(attention_mask)
+        has_pad = (attention_mask == 0).any()
+        has_pad, contiguous = torch.stack([has_pad, contiguous]).tolist()
+        if not has_pad:
+            return None, None
+        assert ps.get_context_model_parallel_world_size() == 1, \
+            "padding masks are not supported under context parallelism"
+        if not contiguous:  # a hole inside a row: no range describes it
+            return attention_mask == 0, None
+        return None, (lo, hi)
+
     def forward(self, input_ids, kv_cache=None, attention_mask=None):
         # input_ids: [b, s(, /cp)] — CP split done by the trainer. With
         # kv_cache, input_ids are the NEW tokens only (decode path).
@@ -343,11 +389,7 @@ class LlamaModel(nn.Module):
             # zigzag CP layout: the two halves of the local chunk are two
             # different global chunks (parallel/cp.py)
             pos_offset = cp_offsets(input_ids.size(1))
-        pad_mask = None
-        if attention_mask is not None and bool((attention_mask == 0).any()):
-            assert ps.get_context_model_parallel_world_size() == 1, \
-                "padding masks are not supported under context parallelism"
-            pad_mask = attention_mask == 0  # [b, s] True at pad keys
+        pad_mask, kv_range = self._padding(attention_mask, kv_cache)
         x = self.embed_tokens(input_ids)  # [b, s, h]
         x = x.transpose(0, 1).contiguous()  # [s, b, h]
         if self.cfg.sequence_parallel:
@@ -356,10 +398,12 @@ class LlamaModel(nn.Module):
         for li, layer in enumerate(self.layers):
             if full_ckpt:
                 x = _ckpt(layer, x, self.rope_cos, self.rope_sin, pos_offset,
-                          use_reentrant=False, pad_mask=pad_mask)
+                          use_reentrant=False, pad_mask=pad_mask,
+                          kv_range=kv_range)
             else:
                 x = layer(x, self.rope_cos, self.rope_sin, pos_offset,
-                          cache=kv_cache, layer_idx=li, pad_mask=pad_mask)
+                          cache=kv_cache, layer_idx=li, pad_mask=pad_mask,
+                          kv_range=kv_range)
         if kv_cache is not None:
             kv_cache.seq_len += input_ids.size(1)
         x = self.norm(x)

@@ -78,7 +78,7 @@ def kernels_for(t: torch.Tensor):
 from .rmsnorm import rmsnorm  # noqa: E402
 from .rope import apply_rotary_pos_emb  # noqa: E402
 from .swiglu import swiglu  # noqa: E402
-from .flash_attn import flash_attn_func  # noqa: E402
+from .flash_attn import flash_attn_func, mask_to_kv_range  # noqa: E402
 
 __all__ = [
     "have_extension",
@@ -88,4 +88,5 @@ __all__ = [
     "apply_rotary_pos_emb",
     "swiglu",
     "flash_attn_func",
+    "mask_to_kv_range",
 ]

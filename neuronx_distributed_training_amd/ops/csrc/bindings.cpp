@@ -31,6 +31,15 @@ void launch_flash_bwd(const void*, const void*, const void*, const void*,
                       const long*, const long*, const long*, hipStream_t);
 void launch_attn_delta(const void*, const void*, void*, int, int, int, int,
                        const long*, const long*, hipStream_t);
+void launch_flash_fwd_range(const void*, const void*, const void*, void*,
+                            void*, int, int, int, int, int, int, bool, float,
+                            int, const long*, const long*, const long*,
+                            const int*, const int*, hipStream_t);
+void launch_flash_bwd_range(const void*, const void*, const void*,
+                            const void*, const void*, const void*, void*,
+                            void*, void*, int, int, int, int, int, int, bool,
+                            float, int, const long*, const long*, const long*,
+                            const long*, const int*, const int*, hipStream_t);
 void launch_mfma_probe(const void*, const void*, void*, hipStream_t);
 void launch_mfma_probe32(const void*, const void*, void*, hipStream_t);
 void launch_flash_fwd_v3(const void*, const void*, const void*, void*, void*,
@@ -328,6 +337,88 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
           dv_mem.permute({1, 2, 0, 3})};
 }
 
+static void check_kv_range(const torch::Tensor& t, const torch::Tensor& q,
+                           const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name,
+              " must be on the same GPU as q");
+  TORCH_CHECK(t.scalar_type() == torch::kInt, name, " must be int32");
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == q.size(0), name,
+              " must have shape [B]");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_range(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo,
+    torch::Tensor kv_hi, bool causal, double scale, long window) {
+  // flash_attn_fwd with a per-batch-row visible key range
+  // [kv_lo[b], kv_hi[b]) (padded batches). Values are trusted to satisfy
+  // 0 <= lo <= hi <= S_kv; the Python op clamps them.
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  check_kv_range(kv_lo, q, "kv_lo");
+  check_kv_range(kv_hi, q, "kv_hi");
+  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
+      D = (int)q.size(3);
+  int HKV = (int)k.size(1), SKV = (int)k.size(2);
+  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
+  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
+  auto o_mem = torch::empty({SQ, B, HQ, D}, q.options());
+  auto lse = torch::empty({B, HQ, SQ}, q.options().dtype(torch::kFloat32));
+  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
+  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
+  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
+  launch_flash_fwd_range(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                         o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, SQ,
+                         SKV, D, causal, (float)scale, (int)window, qs, ks,
+                         vs, kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
+                         cur_stream());
+  return {o_mem.permute({1, 2, 0, 3}), lse};
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_range(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, torch::Tensor kv_lo,
+    torch::Tensor kv_hi, bool causal, double scale, long window) {
+  if (dout.stride(3) != 1) dout = dout.contiguous();
+  check_bhsd(dout, "dout");
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  check_kv_range(kv_lo, q, "kv_lo");
+  check_kv_range(kv_hi, q, "kv_hi");
+  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
+      D = (int)q.size(3);
+  int HKV = (int)k.size(1), SKV = (int)k.size(2);
+  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
+  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
+  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
+  // every q-block / key-block stores its whole slab (zeros where the range
+  // leaves it no work), so torch::empty is safe here too
+  auto dq_mem = torch::empty({SQ, B, HQ, D}, q.options());
+  int group = HQ / HKV;
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto dk_part = torch::empty({group, SKV, B, HKV, D}, f32);
+  auto dv_part = torch::empty({group, SKV, B, HKV, D}, f32);
+  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
+  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
+  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
+  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
+  launch_flash_bwd_range(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                         v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                         dq_mem.data_ptr(), dk_part.data_ptr(),
+                         dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
+                         (float)scale, (int)window, qs, ks, vs, ds,
+                         kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
+                         cur_stream());
+  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
+  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
+  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
+          dv_mem.permute({1, 2, 0, 3})};
+}
+
 torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
                        torch::Tensor tile_expert, torch::Tensor total_rows,
                        bool trans_b) {
@@ -441,6 +532,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_bwd", &flash_attn_bwd, pybind11::arg("dout"),
         pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_range", &flash_attn_fwd_range, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("kv_lo"),
+        pybind11::arg("kv_hi"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
+  m.def("flash_attn_bwd_range", &flash_attn_bwd_range, pybind11::arg("dout"),
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("kv_lo"),
+        pybind11::arg("kv_hi"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("window") = 0);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);

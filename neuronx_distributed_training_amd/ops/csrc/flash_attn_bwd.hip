@@ -11,8 +11,14 @@
 // key tile 64.
 #include "attn_common.h"
 
+// RANGED (both kernels): per-batch-row visible key range
+// [kv_lo[b], kv_hi[b]) on top of the causal / window mask, matching
+// flash_fwd_dbuf_kernel<.., RANGED>. Keys outside the range get dK = dV = 0
+// (their slabs are still written); query rows with no alive key get dQ = 0
+// and contribute nothing. RANGED=false compiles exactly as before and
+// never reads kv_lo / kv_hi.
 // ============================ dK / dV ============================
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool RANGED = false>
 __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -24,7 +30,9 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
                              // even at TP=8 where HKV_local = 1
     int SQ, int SKV, int Bb, int HQ, int HKV, float scale,
     int window, long sQs, long sQb, long sQh, long sKs, long sKb, long sKh,
-    long sVs, long sVb, long sVh, long sDs, long sDb, long sDh) {
+    long sVs, long sVb, long sVh, long sDs, long sDb, long sDh,
+    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED only)
+    const int* __restrict__ kv_hi = nullptr) {
   constexpr int BN = 256;  // keys per block
   // q tile 64 at 145 KB LDS = 1 block/CU. A BM=32 variant (79 KB, 2
   // blocks/CU) measured SLOWER (14.7 vs 12.0 ms) — the kernel is
@@ -50,6 +58,12 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
   const int g = bhg % group;
   const int hkv = (bhg / group) % HKV;
   const int b = bhg / (group * HKV);
+  // wave-uniform visible key range of this batch row
+  int lo = 0, hi = SKV;
+  if constexpr (RANGED) {
+    lo = kv_lo[b];
+    hi = kv_hi[b];
+  }
 
   const bf16* Kp = K + b * sKb + hkv * sKh;
   const bf16* Vp = V + b * sVb + hkv * sVh;
@@ -98,10 +112,15 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const float* Dp = DELTA + ((long)b * HQ + hq) * SQ;
 
     // causal: first q tile containing a row with qcol + coff >= kbase
-    const int ib0 = CAUSAL ? max(0, (kbase - coff) / BM) : 0;
+    // RANGED: the block's alive keys are [klo, khi); none -> no q tile
+    // (the zero accumulators are still stored below)
+    const int klo = RANGED ? max(kbase, lo) : kbase;
+    const int khi = RANGED ? min(kbase + BN, hi) : kbase + BN;
+    const int ib0 = CAUSAL ? max(0, (klo - coff) / BM) : 0;
     int nqb = (SQ + BM - 1) / BM;
     if (CAUSAL && window > 0)
-      nqb = min(nqb, (kbase + BN - 1 + window - coff + BM - 1) / BM);
+      nqb = min(nqb, (khi - 1 + window - coff + BM - 1) / BM);
+    if (RANGED && klo >= khi) nqb = 0;
     for (int ib = ib0; ib < nqb; ++ib) {
       const int qbase = ib * BM;
       {  // stage Q, dO row-major (16B) + transposed (paired b32)
@@ -146,7 +165,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
       __syncthreads();
 
       // causal: skip waves whose keys are all above this q tile
-      if (!CAUSAL || wkey_min <= qbase + BM - 1 + coff) {
+      if ((!CAUSAL || wkey_min <= qbase + BM - 1 + coff) &&
+          (!RANGED || (krow_w < hi && krow_w + 32 > lo))) {
         __bf16* pw = &pT_lds[wid * 32 * VP];
         __bf16* dw = &dsT_lds[wid * 32 * VP];
 #pragma unroll
@@ -173,6 +193,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
           // alive — skip the 3 compare/selects per element (VALU-bound
           // kernel)
           const bool full_patch =
+              (!RANGED || (krow_w >= lo && krow_w + 31 < hi)) &&
               (qbase + nq * 16 + 15 < SQ) && (krow_w + 31 < SKV) &&
               (!CAUSAL || (qbase + nq * 16 + coff >= krow_w + 31)) &&
               (window <= 0 ||
@@ -199,6 +220,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
                             (CAUSAL && qcol + coff < krow);
                 if (CAUSAL && window > 0)
                   dead |= (qcol + coff >= krow + window);
+                if constexpr (RANGED) dead |= (krow < lo) || (krow >= hi);
                 const float p = dead ? 0.f : __expf(st[sb][r] - lse);
                 const float ds = p * (dpt[sb][r] - delta) * scale;
                 const int lrow = sb * 16 + (lane >> 4) * 4 + r;
@@ -251,7 +273,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
 // ============================ dQ ============================
 // NSB: 16-row sub-blocks per wave (see flash_fwd_kernel) — NSB=1 keeps
 // the chip full at TP=8's HQ_local=4
-template <int D, bool CAUSAL, int NSB>
+template <int D, bool CAUSAL, int NSB, bool RANGED = false>
 __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -259,7 +281,9 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     bf16* __restrict__ dQ,  // [s, b, hq, d] contiguous
     int SQ, int SKV, int Bb, int HQ, int HKV, float scale, int window,
     long sQs, long sQb, long sQh, long sKs, long sKb, long sKh, long sVs,
-    long sVb, long sVh, long sDs, long sDb, long sDh) {
+    long sVb, long sVh, long sDs, long sDb, long sDh,
+    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED only)
+    const int* __restrict__ kv_hi = nullptr) {
   constexpr int BM = NSB * 128, BN = 64;  // BN=32 (2 blk/CU) was slower
   const int coff = SKV - SQ;  // bottom-right causal alignment
   constexpr int KP = D + 8;
@@ -280,6 +304,12 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
   const int hq = bh % HQ;
   const int b = bh / HQ;
   const int hkv = hq / (HQ / HKV);
+  // wave-uniform visible key range of this batch row
+  int lo = 0, hi = SKV;
+  if constexpr (RANGED) {
+    lo = kv_lo[b];
+    hi = kv_hi[b];
+  }
 
   const bf16* Qp = Q + b * sQb + hq * sQh;
   const bf16* dOp = dO + b * sDb + hq * sDh;
@@ -335,10 +365,14 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     for (int nj = 0; nj < DN2; ++nj) dqacc32[nj] = f32x16_t{};
   }
 
-  const int kend = CAUSAL ? min(SKV, q0 + BM + coff) : SKV;
+  int kend = CAUSAL ? min(SKV, q0 + BM + coff) : SKV;
+  if constexpr (RANGED) kend = min(kend, hi);
   const int nkb = (kend + BN - 1) / BN;
-  const int jb0 =
+  int jb0 =
       (CAUSAL && window > 0) ? max(0, (q0 + coff - window + 1) / BN) : 0;
+  // tiles wholly below lo are skipped; jb0 >= nkb leaves the loop empty
+  // and the zero dQ accumulators are stored
+  if constexpr (RANGED) jb0 = max(jb0, lo / BN);
   const int wrow_max = qrow_w + NSB * 16 - 1;
 
   auto stage_kv = [&](int jb, int buf) {
@@ -411,6 +445,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
         const int kcol = kbase + nk * 16 + (lane & 15);
         // interior fast path: whole 32-row x 16-key patch alive (see dkv)
         const bool full_patch =
+            (!RANGED ||
+             (kbase + nk * 16 >= lo && kbase + nk * 16 + 15 < hi)) &&
             (kbase + nk * 16 + 15 < SKV) &&
             (!CAUSAL || (kbase + nk * 16 + 15 <= qrow_w + coff)) &&
             (window <= 0 || (kbase + nk * 16 > qrow_w + 31 + coff - window));
@@ -434,6 +470,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
               bool dead = (kcol >= SKV) || (CAUSAL && kcol > qrow + coff);
               if (CAUSAL && window > 0)
                 dead |= (kcol <= qrow + coff - window);
+              if constexpr (RANGED) dead |= (kcol < lo) || (kcol >= hi);
               const float p = dead ? 0.f : __expf(st[sb][r] - lse[sb][r]);
               const float ds = p * (dpt[sb][r] - delta[sb][r]) * scale;
               dsw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 +
@@ -573,6 +610,53 @@ void launch_flash_bwd(const void* dout, const void* q, const void* k,
           (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
           HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
           kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);  \
+  } while (0)
+  if (D == 128) {
+    if (causal) CASE(128, true); else CASE(128, false);
+  } else if (D == 64) {
+    if (causal) CASE(64, true); else CASE(64, false);
+  }
+#undef CASE
+}
+
+// same grids as launch_flash_bwd, RANGED instantiations: kv_lo / kv_hi are
+// device int32 [B] with 0 <= lo <= hi <= SKV
+void launch_flash_bwd_range(const void* dout, const void* q, const void* k,
+                      const void* v, const void* lse, const void* delta,
+                      void* dq, void* dk, void* dv, int B, int HQ, int HKV,
+                      int SQ, int SKV, int D, bool causal, float scale,
+                      int window, const long* qstr, const long* kstr,
+                      const long* vstr, const long* dostr,
+                      const int* kv_lo, const int* kv_hi,
+                      hipStream_t stream) {
+  dim3 blk(512);
+  dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
+  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
+  const int bm = small ? 128 : 256;
+  dim3 gq((SQ + bm - 1) / bm, B * HQ);
+#define CASE(DD, CC)                                                          \
+  do {                                                                        \
+    flash_bwd_dkv_kernel<DD, CC, true><<<gkv, blk, 0, stream>>>(                    \
+        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
+        (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,  \
+        SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],   \
+        kstr[1],                                                              \
+        kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],     \
+        kv_lo, kv_hi);                                                        \
+    if (small)                                                                \
+      flash_bwd_dq_kernel<DD, CC, 1, true><<<gq, blk, 0, stream>>>(                 \
+          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
+          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
+          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
+          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
+          kv_lo, kv_hi);                                                      \
+    else                                                                      \
+      flash_bwd_dq_kernel<DD, CC, 2, true><<<gq, blk, 0, stream>>>(                 \
+          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
+          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
+          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
+          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
+          kv_lo, kv_hi);                                                      \
   } while (0)
   if (D == 128) {
     if (causal) CASE(128, true); else CASE(128, false);

@@ -8,7 +8,13 @@
 // NSB = 16-row sub-blocks per wave: 2 -> BM 256 (the TP<=4 shape), 1 ->
 // BM 128 for small B*HQ launches (TP=8 has HQ_local=4: BM=256 gives 256
 // blocks = 1/CU on the bench shape — half the chip idles).
-template <int D, bool CAUSAL, int NSB>
+//
+// RANGED: per-batch-row visible key range [kv_lo[b], kv_hi[b]) on top of
+// the causal / window mask (padded batches: one contiguous run of real
+// tokens per row). Key-side only; a query row with no alive key stores
+// O = 0 and a finite LSE. The dense instantiations (RANGED=false) compile
+// exactly as before and never read kv_lo / kv_hi.
+template <int D, bool CAUSAL, int NSB, bool RANGED = false>
 __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, bf16* __restrict__ O,
@@ -17,7 +23,9 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     int window,                     // sliding window (<=0: disabled)
     long sQs, long sQb, long sQh,   // Q element strides (seq, batch, head)
     long sKs, long sKb, long sKh,   // K strides
-    long sVs, long sVb, long sVh) { // V strides
+    long sVs, long sVb, long sVh,   // V strides
+    const int* __restrict__ kv_lo = nullptr,   // [B] int32 (RANGED only)
+    const int* __restrict__ kv_hi = nullptr) {
   constexpr int BM = NSB * 128, BN = 64;
   constexpr int KP = D + 8;
   constexpr int VP = BN + 8;
@@ -35,6 +43,12 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
   // S_q != S_kv: causal is BOTTOM-RIGHT aligned (query i sees keys
   // j <= i + SKV - SQ) — the KV-cache decode / ring half-block convention
   const int coff = SKV - SQ;
+  // wave-uniform visible key range of this batch row
+  int lo = 0, hi = SKV;
+  if constexpr (RANGED) {
+    lo = kv_lo[b];
+    hi = kv_hi[b];
+  }
 
   const bf16* Qp = Q + b * sQb + hq * sQh;
   const bf16* Kp = K + b * sKb + hkv * sKh;
@@ -82,10 +96,14 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     for (int nj = 0; nj < DN; ++nj) oacc[sb][nj] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   }
 
-  const int kend = CAUSAL ? min(SKV, q0 + BM + coff) : SKV;
+  int kend = CAUSAL ? min(SKV, q0 + BM + coff) : SKV;
+  if constexpr (RANGED) kend = min(kend, hi);
   const int nkb = (kend + BN - 1) / BN;
-  const int jb0 =
+  int jb0 =
       (CAUSAL && window > 0) ? max(0, (q0 + coff - window + 1) / BN) : 0;
+  // tiles wholly below lo are skipped; jb0 >= nkb (no alive tile) leaves
+  // the loop empty and the epilogue stores O = 0 / LSE = -1e30
+  if constexpr (RANGED) jb0 = max(jb0, lo / BN);
   const int wrow_max = qrow_w + NSB * 16 - 1;
 
   // T5 static form: the younger dispatch half gets priority so it is not
@@ -100,6 +118,12 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
   constexpr int KV_PER_THR = BN * D / 8 / 512;  // int4 K vectors / thread
   int4 kreg[KV_PER_THR];
   int4 vreg0, vreg1;
+  // V stages as BN*D/16 row-pair slices, one per thread: all 512 threads
+  // at D=128, only the first 256 at D=64 (the rest would fetch rows past
+  // the tile and write them over the V^T image)
+  constexpr int V_SLICES = BN * D / 16;
+  static_assert(V_SLICES <= 512, "one V row-pair slice per thread");
+  const bool v_stager = (V_SLICES == 512) || (threadIdx.x < V_SLICES);
 
   auto issue_loads = [&](int kbase) {
 #pragma unroll
@@ -111,8 +135,8 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
       kreg[u] = (gr < SKV) ? *(const int4*)(Kp + (long)gr * sKs + col8)
                            : int4{0, 0, 0, 0};
     }
-    {
-      const int t = threadIdx.x;  // BN*D/16 == 512 row-pair slices
+    if (v_stager) {
+      const int t = threadIdx.x;
       const int row = (t / (D / 8)) * 2;
       const int col8 = (t % (D / 8)) * 8;
       const int g0 = kbase + row, g1 = g0 + 1;
@@ -131,7 +155,7 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
       const int col8 = (t % (D / 8)) * 8;
       *(int4*)&k_lds[buf][row * KP + col8] = kreg[u];
     }
-    {
+    if (v_stager) {
       const int t = threadIdx.x;
       const int row = (t / (D / 8)) * 2;
       const int col8 = (t % (D / 8)) * 8;
@@ -179,6 +203,7 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
       for (int sb = 0; sb < NSB; ++sb) {
         // interior tiles (every key visible to every row) skip the mask
         const bool full_tile =
+            (!RANGED || (kbase >= lo && kbase + BN <= hi)) &&
             (kbase + BN <= SKV) &&
             (!CAUSAL || (kbase + BN - 1 <= qrow_w + sb * 16 + coff)) &&
             (window <= 0 || kbase >= qrow_w + sb * 16 + coff + 15 - window + 1);
@@ -204,6 +229,7 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
               float s = sacc[sb][nk][r];  // scale folded into Q
               bool dead = (kcol >= SKV) || (CAUSAL && kcol > qrow + coff);
               if (CAUSAL && window > 0) dead |= (kcol <= qrow + coff - window);
+              if constexpr (RANGED) dead |= (kcol < lo) || (kcol >= hi);
               s = dead ? -1e30f : s;
               sv[nk][r] = s;
               tile_max[r] = fmaxf(tile_max[r], s);
@@ -242,7 +268,11 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
         for (int nk = 0; nk < 4; ++nk) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = __expf(sv[nk][r] - m_i[sb][r]);
+            float p = __expf(sv[nk][r] - m_i[sb][r]);
+            // a row with no alive key yet still has m_i = -1e30, so its
+            // dead entries would get exp(0) = 1 (dense causal rows always
+            // see themselves; rows below lo do not) — force them to 0
+            if constexpr (RANGED) p = (sv[nk][r] < -1e29f) ? 0.f : p;
             pw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 + (lane & 15)] =
                 (__bf16)p;
           }
@@ -334,6 +364,42 @@ void launch_flash_fwd_dbuf(const void* q, const void* k, const void* v, void* o,
           (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
           (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
           qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2]);     \
+  } while (0)
+  if (D == 128) {
+    if (causal) CASE(128, true); else CASE(128, false);
+  } else if (D == 64) {
+    if (causal) CASE(64, true); else CASE(64, false);
+  }
+#undef CASE
+}
+
+// same tiling rule as launch_flash_fwd_dbuf, RANGED instantiations:
+// kv_lo / kv_hi are device int32 [B] with 0 <= lo <= hi <= SKV
+void launch_flash_fwd_range(const void* q, const void* k, const void* v, void* o,
+                      void* lse, int B, int HQ, int HKV, int SQ, int SKV,
+                      int D, bool causal, float scale, int window,
+                      const long* qstr, const long* kstr, const long* vstr,
+                      const int* kv_lo, const int* kv_hi,
+                      hipStream_t stream) {
+  // BM=128 when the BM=256 grid would leave CUs idle (TP=8: HQ_local=4)
+  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
+  const int bm = small ? 128 : 256;
+  dim3 grid((SQ + bm - 1) / bm, B * HQ);
+  dim3 blk(512);
+#define CASE(DD, CC)                                                          \
+  do {                                                                        \
+    if (small)                                                                \
+      flash_fwd_dbuf_kernel<DD, CC, 1, true><<<grid, blk, 0, stream>>>(                  \
+          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
+          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
+          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
+          kv_lo, kv_hi);                                                      \
+    else                                                                      \
+      flash_fwd_dbuf_kernel<DD, CC, 2, true><<<grid, blk, 0, stream>>>(                  \
+          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
+          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
+          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
+          kv_lo, kv_hi);                                                      \
   } while (0)
   if (D == 128) {
     if (causal) CASE(128, true); else CASE(128, false);

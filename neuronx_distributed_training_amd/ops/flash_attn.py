@@ -11,6 +11,12 @@ recompute backward (FlashAttention-2 style two-kernel dKV/dQ backward).
 
 CPU path: exact fp32 reference via scaled_dot_product_attention (tests
 compare the HIP kernel against this).
+
+Padded batches: ``kv_range=(kv_lo, kv_hi)`` gives every batch row a visible
+key range ``[kv_lo[b], kv_hi[b])`` on top of the causal / window mask
+(key-side only). A query row with no alive key gets O = 0, dQ = 0 and a
+finite LSE; keys outside the range get dK = dV = 0. Ranged calls always run
+the v2 kernels.
 """
 
 from __future__ import annotations
@@ -50,7 +56,51 @@ def _bwd_fn(kern, sq=None, skv=None):
     return kern.flash_attn_bwd
 
 
-def _make_mask(sq, sk, causal, window, device):
+def mask_to_kv_range_tensors(attention_mask):
+    """Device-side part of :func:`mask_to_kv_range`: returns int32
+    ``kv_lo``, ``kv_hi`` [B] and a 0-dim bool tensor ``contiguous`` without
+    a host sync."""
+    m = attention_mask != 0
+    s = m.size(1)
+    mi = m.to(torch.int32)
+    has = m.any(dim=1)
+    lo = torch.argmax(mi, dim=1)                     # first non-zero
+    hi = s - torch.argmax(mi.flip(1), dim=1)         # one past the last
+    zero = torch.zeros_like(lo)
+    lo = torch.where(has, lo, zero)
+    hi = torch.where(has, hi, zero)                  # all-zero row: lo == hi
+    contiguous = (mi.sum(dim=1) == hi - lo).all()
+    return lo.to(torch.int32), hi.to(torch.int32), contiguous
+
+
+def mask_to_kv_range(attention_mask):
+    """[B, S] padding mask (non-zero = real token) -> (kv_lo, kv_hi,
+    contiguous). ``[kv_lo[b], kv_hi[b])`` spans the first to the last real
+    token of row b (``lo == hi`` for a row of all zeros); ``contiguous`` is
+    False if any row has a hole inside that span, in which case the range
+    does not describe the mask."""
+    lo, hi, contiguous = mask_to_kv_range_tensors(attention_mask)
+    return lo, hi, bool(contiguous)
+
+
+def _norm_kv_range(kv_range, b, skv, device):
+    """Clamp to 0 <= lo <= hi <= S_kv (the kernels trust this) and make the
+    pair contiguous int32 [B] on `device`."""
+    lo, hi = kv_range
+    lo = torch.as_tensor(lo, device=device).to(torch.int32).reshape(-1)
+    hi = torch.as_tensor(hi, device=device).to(torch.int32).reshape(-1)
+    if lo.numel() != b or hi.numel() != b:
+        raise ValueError(
+            f"kv_range tensors must have shape [{b}], got "
+            f"{tuple(lo.shape)} / {tuple(hi.shape)}"
+        )
+    hi = hi.clamp(0, skv)
+    lo = torch.minimum(lo.clamp(0, skv), hi)
+    return lo.contiguous(), hi.contiguous()
+
+
+def _make_mask(sq, sk, causal, window, device, kv_lo=None, kv_hi=None):
+    """True = dead. [sq, sk], or [b, 1, sq, sk] with a key range."""
     # S_q != S_kv: bottom-right alignment (query i sees keys
     # j <= i + sk - sq) — matches the HIP kernel's decode convention
     mask = torch.zeros(sq, sk, dtype=torch.bool, device=device)
@@ -63,36 +113,70 @@ def _make_mask(sq, sk, causal, window, device):
             mask |= torch.ones(sq, sk, dtype=torch.bool, device=device).tril(
                 diag - window
             )
+    if kv_lo is not None:
+        j = torch.arange(sk, device=device)
+        out = (j[None, :] < kv_lo[:, None]) | (j[None, :] >= kv_hi[:, None])
+        mask = mask[None, None] | out[:, None, None, :]
     return mask
 
 
-def _cpu_ref_fwd(q, k, v, causal, scale, window=0):
+def _ranged_softmax(s, mask):
+    """softmax over alive keys; rows with no alive key give p = 0 exactly
+    (no NaN from an all -inf row) and LSE = -1e30 like the kernel."""
+    s = s.masked_fill(mask, float("-inf"))
+    m = s.amax(dim=-1, keepdim=True)
+    empty = torch.isinf(m)
+    m = torch.where(empty, torch.zeros_like(m), m)
+    e = torch.exp(s - m)                             # dead -> exactly 0
+    l = e.sum(dim=-1, keepdim=True)
+    p = e / torch.where(empty, torch.ones_like(l), l)
+    lse = torch.where(empty, torch.full_like(m, -1e30), m + torch.log(l))
+    return p, lse.squeeze(-1)
+
+
+def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None):
     hq, hkv = q.size(1), k.size(1)
     if hq != hkv:
         k = k.repeat_interleave(hq // hkv, dim=1)
         v = v.repeat_interleave(hq // hkv, dim=1)
     qf, kf, vf = q.float(), k.float(), v.float()
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
-    mask = _make_mask(q.size(-2), k.size(-2), causal, window, q.device)
-    s = s.masked_fill(mask, float("-inf"))
-    lse = torch.logsumexp(s, dim=-1)
-    p = torch.softmax(s, dim=-1)
+    mask = _make_mask(q.size(-2), k.size(-2), causal, window, q.device,
+                      kv_lo, kv_hi)
+    if kv_lo is not None:
+        p, lse = _ranged_softmax(s, mask)
+    else:
+        s = s.masked_fill(mask, float("-inf"))
+        lse = torch.logsumexp(s, dim=-1)
+        p = torch.softmax(s, dim=-1)
     o = torch.matmul(p, vf)
     return o.to(q.dtype), lse
 
 
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal: bool, scale: float, window: int = 0):
+    def forward(ctx, q, k, v, causal: bool, scale: float, window: int = 0,
+                kv_lo=None, kv_hi=None):
         kern = kernels_for(q)
-        if kern is not None:
+        ranged = kv_lo is not None
+        if kern is not None and ranged:
+            # ranged calls always use the v2 kernels (like S_q != S_kv)
+            o, lse = kern.flash_attn_fwd_range(
+                q, k, v, kv_lo, kv_hi, causal, scale, window
+            )
+        elif kern is not None:
             # kernel takes arbitrary-strided [b, h, s, d] views (d contig)
             o, lse = _fwd_fn(kern, q.size(2), k.size(2))(
                 q, k, v, causal, scale, window
             )
         else:
-            o, lse = _cpu_ref_fwd(q, k, v, causal, scale, window)
-        ctx.save_for_backward(q, k, v, o, lse)
+            o, lse = _cpu_ref_fwd(q, k, v, causal, scale, window,
+                                  kv_lo, kv_hi)
+        if ranged:
+            ctx.save_for_backward(q, k, v, o, lse, kv_lo, kv_hi)
+        else:
+            ctx.save_for_backward(q, k, v, o, lse)
+        ctx.ranged = ranged
         ctx.causal = causal
         ctx.scale = scale
         ctx.window = window
@@ -100,13 +184,23 @@ class _FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, o, lse = ctx.saved_tensors
+        kv_lo = kv_hi = None
+        if ctx.ranged:
+            q, k, v, o, lse, kv_lo, kv_hi = ctx.saved_tensors
+        else:
+            q, k, v, o, lse = ctx.saved_tensors
         kern = kernels_for(q)
+        if kern is not None and ctx.ranged:
+            dq, dk, dv = kern.flash_attn_bwd_range(
+                do, q, k, v, o, lse, kv_lo, kv_hi, ctx.causal, ctx.scale,
+                ctx.window,
+            )
+            return dq, dk, dv, None, None, None, None, None
         if kern is not None:
             dq, dk, dv = _bwd_fn(kern, q.size(2), k.size(2))(
                 do, q, k, v, o, lse, ctx.causal, ctx.scale, ctx.window
             )
-            return dq, dk, dv, None, None, None
+            return dq, dk, dv, None, None, None, None, None
         # CPU reference backward (fp32, explicit)
         hq, hkv = q.size(1), k.size(1)
         g = hq // hkv
@@ -114,9 +208,13 @@ class _FlashAttnFn(torch.autograd.Function):
         vx = v.repeat_interleave(g, dim=1).float()
         qf, dof = q.float(), do.float()
         s = torch.matmul(qf, kx.transpose(-1, -2)) * ctx.scale
-        mask = _make_mask(q.size(-2), k.size(-2), ctx.causal, ctx.window, q.device)
-        s = s.masked_fill(mask, float("-inf"))
-        p = torch.softmax(s, dim=-1)
+        mask = _make_mask(q.size(-2), k.size(-2), ctx.causal, ctx.window,
+                          q.device, kv_lo, kv_hi)
+        if ctx.ranged:
+            p, _ = _ranged_softmax(s, mask)
+        else:
+            s = s.masked_fill(mask, float("-inf"))
+            p = torch.softmax(s, dim=-1)
         dv = torch.matmul(p.transpose(-1, -2), dof)
         dp = torch.matmul(dof, vx.transpose(-1, -2))
         delta = (dof * o.float()).sum(-1, keepdim=True)
@@ -126,7 +224,8 @@ class _FlashAttnFn(torch.autograd.Function):
         if g > 1:
             dk = dk.reshape(dk.size(0), hkv, g, dk.size(-2), dk.size(-1)).sum(2)
             dv = dv.reshape(dv.size(0), hkv, g, dv.size(-2), dv.size(-1)).sum(2)
-        return dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None, None
+        return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None,
+                None, None, None)
 
 
 def flash_attn_func(
@@ -136,9 +235,19 @@ def flash_attn_func(
     causal: bool = True,
     scale: float | None = None,
     window: int | None = None,
+    kv_range=None,
 ) -> torch.Tensor:
     """window: sliding-window size (attend to the last `window` keys);
-    None/0 disables (Mixtral sliding_window parity)."""
+    None/0 disables (Mixtral sliding_window parity).
+
+    kv_range: optional pair ``(kv_lo, kv_hi)`` of int tensors [B]; batch
+    row b only sees keys ``kv_lo[b] <= j < kv_hi[b]`` (see
+    :func:`mask_to_kv_range`). None = dense attention."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.size(-1))
-    return _FlashAttnFn.apply(q, k, v, causal, scale, int(window or 0))
+    if kv_range is None:
+        return _FlashAttnFn.apply(q, k, v, causal, scale, int(window or 0))
+    kv_lo, kv_hi = _norm_kv_range(kv_range, q.size(0), k.size(2), q.device)
+    return _FlashAttnFn.apply(
+        q, k, v, causal, scale, int(window or 0), kv_lo, kv_hi
+    )

@@ -325,6 +325,7 @@ class LlamaModule(BaseModelModule):
             fuse_qkv=bool(mcfg.get("fuse_qkv", True)),
             activation_checkpoint=mcfg.get("activation_checkpoint"),
             sliding_window=mcfg.get("sliding_window"),
+            padded_attention=str(mcfg.get("padded_attention", "auto")),
             tie_word_embeddings=bool(mcfg.get("tie_word_embeddings", False)),
             dtype=dtype,
         )
