@@ -74,6 +74,7 @@ std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
   CHECK_IN(x);
   CHECK_IN(w);
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "rmsnorm: bf16 only");
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "rmsnorm: w must be bf16");
   auto N = x.size(0);
   auto H = x.size(1);
   TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
@@ -88,6 +89,8 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor invrms) {
   CHECK_IN(dy);
   CHECK_IN(x);
+  CHECK_IN(w);
+  TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "rmsnorm: w must be bf16");
   auto N = x.size(0);
   auto H = x.size(1);
   auto dx = torch::empty_like(x);
@@ -174,6 +177,29 @@ static void check_bhsd(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
 }
 
+// Shared argument contract of the three backward bindings. The kernels
+// index LSE as a dense [B, HQ, SQ] fp32 array (no strides), so a view such
+// as the ring's lse[:, :, half:] is copied (B*HQ*SQ floats); returns the
+// LSE to hand to the kernel.
+static torch::Tensor check_bwd_args(const torch::Tensor& q,
+                                    const torch::Tensor& k,
+                                    const torch::Tensor& v,
+                                    const torch::Tensor& lse) {
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  TORCH_CHECK(q.size(3) == 128 || q.size(3) == 64,
+              "head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(1) > 0 && q.size(1) % k.size(1) == 0,
+              "GQA head mismatch");
+  TORCH_CHECK(lse.is_cuda() && lse.device() == q.device(),
+              "lse must be on the same GPU as q");
+  TORCH_CHECK(lse.scalar_type() == torch::kFloat32, "lse must be fp32");
+  TORCH_CHECK(lse.dim() == 3 && lse.size(0) == q.size(0) &&
+                  lse.size(1) == q.size(1) && lse.size(2) == q.size(2),
+              "lse must have shape [B, HQ, SQ]");
+  return lse.contiguous();
+}
+
 static torch::Tensor attn_delta(torch::Tensor dout, torch::Tensor o) {
   // fused rowsum(dO . O) -> [B, HQ, SQ] fp32 (no fp32 materialization)
   auto oc = o.stride(3) == 1 ? o : o.contiguous();
@@ -220,9 +246,11 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
+  lse = check_bwd_args(q, k, v, lse);
   int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
       D = (int)q.size(3);
   int HKV = (int)k.size(1);
+  TORCH_CHECK(k.size(2) == S, "v3 kernel requires S_q == S_kv (use v2)");
   auto delta = attn_delta(dout, o);
   auto dq_mem = torch::empty({S, B, HQ, D}, q.options());
   int group = HQ / HKV;
@@ -289,13 +317,14 @@ std::vector<torch::Tensor> flash_attn_fwd_sbuf(torch::Tensor q,
       D = (int)q.size(3);
   int HKV = (int)k.size(1), SKV = (int)k.size(2);
   TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
   TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
   auto o_mem = torch::empty({SQ, B, HQ, D}, q.options());
   auto lse = torch::empty({B, HQ, SQ}, q.options().dtype(torch::kFloat32));
   long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
   long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
   long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  launch_flash_fwd_dbuf(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+  launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
                         o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, SQ,
                         SKV, D, causal, (float)scale, (int)window, qs, ks,
                         vs, cur_stream());
@@ -310,6 +339,7 @@ std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
+  lse = check_bwd_args(q, k, v, lse);
   int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
       D = (int)q.size(3);
   int HKV = (int)k.size(1), SKV = (int)k.size(2);
@@ -384,15 +414,12 @@ std::vector<torch::Tensor> flash_attn_bwd_range(
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
+  lse = check_bwd_args(q, k, v, lse);
   check_kv_range(kv_lo, q, "kv_lo");
   check_kv_range(kv_hi, q, "kv_hi");
   int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
       D = (int)q.size(3);
   int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
   TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
   auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
   // every q-block / key-block stores its whole slab (zeros where the range

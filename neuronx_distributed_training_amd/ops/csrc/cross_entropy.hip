@@ -17,7 +17,9 @@ __global__ void ce_fwd_kernel(const bf16* __restrict__ logits,
                               long vocab_start) {
   const int row = blockIdx.x;
   const bf16* lr = logits + (long)row * V;
-  const int nvec = V >> 3;
+  // 16-byte vector loads need every row 16-byte aligned: only V % 8 == 0
+  // gives that; any other V takes the scalar loop for the whole row
+  const int nvec = (V & 7) ? 0 : (V >> 3);
   // online max+sum per thread
   float m = -1e30f, s = 0.f;
   for (int i = threadIdx.x; i < nvec; i += NT) {
@@ -32,7 +34,7 @@ __global__ void ce_fwd_kernel(const bf16* __restrict__ logits,
       m = mn;
     }
   }
-  // tail (V % 8)
+  // scalar path (whole row when V % 8 != 0)
   for (int i = (nvec << 3) + threadIdx.x; i < V; i += NT) {
     float a = bf2f(lr[i]);
     float mn = fmaxf(m, a);
@@ -86,7 +88,7 @@ __global__ void ce_bwd_kernel(const bf16* __restrict__ logits,
   const float inv_s = 1.f / gsum[row];
   const float go = gout[row];
   const long t = targets[row] - vocab_start;
-  const int nvec = V >> 3;
+  const int nvec = (V & 7) ? 0 : (V >> 3);  // see ce_fwd_kernel
   for (int i = threadIdx.x; i < nvec; i += NT) {
     Pack16B p, o;
     p.i4 = ((const int4*)lr)[i];

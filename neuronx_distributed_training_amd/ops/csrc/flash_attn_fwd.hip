@@ -108,6 +108,12 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
   constexpr int KV_PER_THR = BN * D / 8 / 512;  // int4 K vectors / thread
   int4 kreg[KV_PER_THR];
   int4 vreg0, vreg1;
+  // V stages as BN*D/16 row-pair slices, one per thread: all 512 threads
+  // at D=128, only the first 256 at D=64 (the rest would fetch rows past
+  // the tile and write them over the V^T image)
+  constexpr int V_SLICES = BN * D / 16;
+  static_assert(V_SLICES <= 512, "one V row-pair slice per thread");
+  const bool v_stager = (V_SLICES == 512) || (threadIdx.x < V_SLICES);
 
   auto issue_loads = [&](int kbase) {
 #pragma unroll
@@ -119,8 +125,8 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
       kreg[u] = (gr < SKV) ? *(const int4*)(Kp + (long)gr * sKs + col8)
                            : int4{0, 0, 0, 0};
     }
-    {
-      const int t = threadIdx.x;  // BN*D/16 == 512 row-pair slices
+    if (v_stager) {
+      const int t = threadIdx.x;
       const int row = (t / (D / 8)) * 2;
       const int col8 = (t % (D / 8)) * 8;
       const int g0 = kbase + row, g1 = g0 + 1;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
       const int col8 = (t % (D / 8)) * 8;
       *(int4*)&k_lds[row * KP + col8] = kreg[u];
     }
-    {
+    if (v_stager) {
       const int t = threadIdx.x;
       const int row = (t / (D / 8)) * 2;
       const int col8 = (t % (D / 8)) * 8;

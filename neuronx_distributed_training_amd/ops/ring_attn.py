@@ -109,6 +109,51 @@ def _bwd_block(kern, do, q, k, v, out, lse, causal, scale):
     return _cpu_block_bwd(do, q, k, v, out, lse, causal, scale)
 
 
+def _ring_fwd_hop(kern, r, j, q, k_blk, v_blk, acc_o, acc_lse, scale):
+    """One forward hop of rank ``r`` against ring peer ``j``'s K/V block:
+    picks the zigzag case, slices, runs the block kernel and merges the
+    partial into the fp32 accumulators (in place)."""
+    half = q.size(2) // 2
+    if j == r:
+        o, lse = _fwd_block(kern, q, k_blk, v_blk, True, scale)
+        _merge_into(acc_o, acc_lse, o, lse)
+    elif j < r:
+        o, lse = _fwd_block(
+            kern, q, k_blk[:, :, :half], v_blk[:, :, :half], False, scale,
+        )
+        _merge_into(acc_o, acc_lse, o, lse)
+    else:  # j > r: only the high-half queries see this block
+        o, lse = _fwd_block(kern, q[:, :, half:], k_blk, v_blk, False, scale)
+        _merge_into(acc_o[:, :, half:], acc_lse[:, :, half:], o, lse)
+
+
+def _ring_bwd_hop(kern, r, j, dout, q, k_blk, v_blk, out, lse, dq_acc, scale):
+    """One backward hop of rank ``r`` against ring peer ``j``'s K/V block,
+    with the GLOBAL merged ``lse`` and ``out``. Adds this block's dQ into
+    ``dq_acc`` (in place) and returns ``(dk_j, dv_j, lo_only)``; with
+    ``lo_only`` the gradients cover only the block's LOW half."""
+    half = q.size(2) // 2
+    lo_only = j < r  # only this block's LOW chunk was visible
+    if j == r:
+        dq_j, dk_j, dv_j = _bwd_block(
+            kern, dout, q, k_blk, v_blk, out, lse, True, scale
+        )
+        dq_acc += dq_j
+    elif j < r:
+        dq_j, dk_j, dv_j = _bwd_block(
+            kern, dout, q, k_blk[:, :, :half], v_blk[:, :, :half],
+            out, lse, False, scale,
+        )
+        dq_acc += dq_j
+    else:  # j > r
+        dq_j, dk_j, dv_j = _bwd_block(
+            kern, dout[:, :, half:], q[:, :, half:], k_blk, v_blk,
+            out[:, :, half:], lse[:, :, half:], False, scale,
+        )
+        dq_acc[:, :, half:] += dq_j
+    return dk_j, dv_j, lo_only
+
+
 class _RingFlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
@@ -117,7 +162,6 @@ class _RingFlashAttnFn(torch.autograd.Function):
         kern = kernels_for(q)
         s_loc = q.size(2)
         assert s_loc % 2 == 0, "zigzag CP needs an even local sequence"
-        half = s_loc // 2
         k_cur, v_cur = k.contiguous(), v.contiguous()
         # TWO fresh recv buffers: the ping-pong must never receive into the
         # original k/v (they are saved for backward — aliasing them
@@ -130,7 +174,6 @@ class _RingFlashAttnFn(torch.autograd.Function):
             (q.size(0), q.size(1), s_loc), -1e30,
             dtype=torch.float32, device=q.device,
         )
-        q_hi = q[:, :, half:]
         with torch.no_grad():
             for t in range(R):
                 j = (r - t) % R
@@ -139,20 +182,9 @@ class _RingFlashAttnFn(torch.autograd.Function):
                     works = _post_shift(
                         (k_cur, v_cur), (k_bufs[t % 2], v_bufs[t % 2])
                     )
-                if j == r:
-                    o, lse = _fwd_block(kern, q, k_cur, v_cur, True, scale)
-                    _merge_into(acc_o, acc_lse, o, lse)
-                elif j < r:
-                    o, lse = _fwd_block(
-                        kern, q, k_cur[:, :, :half], v_cur[:, :, :half],
-                        False, scale,
-                    )
-                    _merge_into(acc_o, acc_lse, o, lse)
-                else:  # j > r: only the high-half queries see this block
-                    o, lse = _fwd_block(kern, q_hi, k_cur, v_cur, False, scale)
-                    _merge_into(
-                        acc_o[:, :, half:], acc_lse[:, :, half:], o, lse
-                    )
+                _ring_fwd_hop(
+                    kern, r, j, q, k_cur, v_cur, acc_o, acc_lse, scale
+                )
                 for w in works:
                     w.wait()
                 if t < R - 1:
@@ -183,8 +215,6 @@ class _RingFlashAttnFn(torch.autograd.Function):
         dv_buf = torch.empty_like(dv_cur)
         dq_acc = torch.zeros_like(q)
 
-        do_hi, q_hi = dout[:, :, half:], q[:, :, half:]
-        o_hi, lse_hi = out[:, :, half:], lse[:, :, half:]
         acc_works: List = []
         for t in range(R):
             j = (r - t) % R
@@ -194,24 +224,9 @@ class _RingFlashAttnFn(torch.autograd.Function):
                 kv_works = _post_shift(
                     (k_cur, v_cur), (k_bufs[t % 2], v_bufs[t % 2])
                 )
-            lo_only = j < r  # only this block's LOW chunk was visible
-            if j == r:
-                dq_j, dk_j, dv_j = _bwd_block(
-                    kern, dout, q, k_cur, v_cur, out, lse, True, scale
-                )
-                dq_acc += dq_j
-            elif j < r:
-                dq_j, dk_j, dv_j = _bwd_block(
-                    kern, dout, q, k_cur[:, :, :half], v_cur[:, :, :half],
-                    out, lse, False, scale,
-                )
-                dq_acc += dq_j
-            else:  # j > r
-                dq_j, dk_j, dv_j = _bwd_block(
-                    kern, do_hi, q_hi, k_cur, v_cur, o_hi, lse_hi,
-                    False, scale,
-                )
-                dq_acc[:, :, half:] += dq_j
+            dk_j, dv_j, lo_only = _ring_bwd_hop(
+                kern, r, j, dout, q, k_cur, v_cur, out, lse, dq_acc, scale
+            )
             # fold into the accumulator that traveled with this block
             for w in acc_works:
                 w.wait()

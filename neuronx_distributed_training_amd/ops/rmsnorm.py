@@ -14,6 +14,14 @@ import torch
 from . import kernels_for
 
 
+def _kernel_weight(weight: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """The kernels read the weight as bf16 (the binding rejects anything
+    else). A weight kept in another dtype — RMSNorm's default is fp32, and
+    "autocast" precision keeps fp32 parameters — is cast to the activation
+    dtype for the kernel; its gradient is returned in its own dtype."""
+    return weight if weight.dtype == x.dtype else weight.to(x.dtype)
+
+
 class _RMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, eps: float):
@@ -21,7 +29,9 @@ class _RMSNormFn(torch.autograd.Function):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         if k is not None:
-            y, invrms = k.rmsnorm_fwd(x2.contiguous(), weight, eps)
+            y, invrms = k.rmsnorm_fwd(
+                x2.contiguous(), _kernel_weight(weight, x2), eps
+            )
         else:
             xf = x2.float()
             invrms = torch.rsqrt(xf.pow(2).mean(-1) + eps)
@@ -36,7 +46,10 @@ class _RMSNormFn(torch.autograd.Function):
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         k = kernels_for(dy2)
         if k is not None:
-            dx, dw = k.rmsnorm_bwd(dy2, x2.contiguous(), weight, invrms)
+            dx, dw = k.rmsnorm_bwd(
+                dy2, x2.contiguous(), _kernel_weight(weight, x2), invrms
+            )
+            dw = dw.to(weight.dtype)
         else:
             xf = x2.float()
             dyf = dy2.float()
