@@ -453,12 +453,20 @@ torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
   // trans_b=false: C = a @ w[e]^T ([Tp, N]); true: C = a @ w[e] ([Tp, Kw]).
   CHECK_IN(a);
   CHECK_IN(w);
+  CHECK_IN(tile_expert);
+  CHECK_IN(total_rows);
+  TORCH_CHECK(a.dim() == 2, "moe_gemm: a must be [Tp, K]");
+  TORCH_CHECK(w.dim() == 3, "moe_gemm: w must be [E, N, Kw]");
   TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
                   w.scalar_type() == torch::kBFloat16,
               "moe_gemm: bf16 only");
   TORCH_CHECK(tile_expert.scalar_type() == torch::kInt &&
                   total_rows.scalar_type() == torch::kInt,
               "moe_gemm: int32 maps");
+  TORCH_CHECK(w.device() == a.device() && tile_expert.device() == a.device() &&
+                  total_rows.device() == a.device(),
+              "moe_gemm: w and the int32 maps must be on a's device");
+  TORCH_CHECK(total_rows.numel() == 1, "moe_gemm: total_rows must be [1]");
   long Tp = a.size(0);
   int K = (int)a.size(1);
   int N = (int)w.size(1), Kw = (int)w.size(2);
@@ -467,7 +475,11 @@ torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
   int contraction = trans_b ? N : Kw;
   int out_cols = trans_b ? Kw : N;
   TORCH_CHECK(K == contraction, "moe_gemm: contraction mismatch");
+  // 16-byte row loads of a and w need every row start 16-byte aligned
+  TORCH_CHECK(K % 8 == 0, "moe_gemm: contraction % 8");
   TORCH_CHECK(out_cols % 128 == 0, "moe_gemm: out cols % 128");
+  TORCH_CHECK(tile_expert.numel() >= row_tiles,
+              "moe_gemm: tile_expert shorter than Tp / 256");
   auto c = torch::empty({Tp, out_cols}, a.options());
   launch_moe_gemm(a.data_ptr(), w.data_ptr(), c.data_ptr(),
                   tile_expert.data_ptr<int>(), total_rows.data_ptr<int>(),
@@ -481,7 +493,20 @@ torch::Tensor moe_wgrad(torch::Tensor dy, torch::Tensor x,
   // dW[e] = dy[seg_e]^T @ x[seg_e] -> [E, N, K] fp32
   CHECK_IN(dy);
   CHECK_IN(x);
+  CHECK_IN(seg_start);
+  TORCH_CHECK(dy.dim() == 2 && x.dim() == 2,
+              "moe_wgrad: dy must be [Tp, N] and x [Tp, K]");
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
+                  x.scalar_type() == torch::kBFloat16,
+              "moe_wgrad: bf16 only");
   TORCH_CHECK(seg_start.scalar_type() == torch::kInt, "int32 seg bounds");
+  TORCH_CHECK(x.device() == dy.device() && seg_start.device() == dy.device(),
+              "moe_wgrad: x and seg_start must be on dy's device");
+  TORCH_CHECK(dy.size(0) == x.size(0), "moe_wgrad: dy and x row counts differ");
+  // the kernel walks each segment in 32-row chunks
+  TORCH_CHECK(dy.size(0) % 32 == 0, "moe_wgrad: rows % 32");
+  TORCH_CHECK(E >= 1 && seg_start.numel() == E + 1,
+              "moe_wgrad: seg_start must have E + 1 entries");
   int N = (int)dy.size(1), K = (int)x.size(1);
   TORCH_CHECK(N % 128 == 0 && K % 128 == 0, "moe_wgrad: dims % 128");
   auto dw = torch::empty({E, N, K}, dy.options().dtype(torch::kFloat32));

@@ -90,8 +90,13 @@ def grouped_expert_mlp(x: torch.Tensor, counts: torch.Tensor,
 
 
 def grouped_path_supported(x, gate_up, down) -> bool:
-    if kernels_for(x) is None or x.dtype != torch.bfloat16:
+    if kernels_for(x) is None:
         return False
+    # the kernels take bf16, contiguous operands only (under autocast the
+    # parameters stay fp32: that case belongs to the library path)
+    for t in (x, gate_up, down):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous():
+            return False
     H = x.size(1)
     I2, I = gate_up.size(1), down.size(2)
     return H % 128 == 0 and I2 % 128 == 0 and I % 128 == 0

@@ -14,6 +14,11 @@ import torch.nn.functional as F
 from . import kernels_for
 
 
+def _ref_dtype(t: torch.Tensor) -> torch.dtype:
+    # CPU reference path: fp32 for bf16/fp16/fp32 inputs, fp64 stays fp64
+    return torch.promote_types(t.dtype, torch.float32)
+
+
 class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gate_up: torch.Tensor):
@@ -24,7 +29,7 @@ class _SwiGLUFn(torch.autograd.Function):
                 *gate_up.shape[:-1], gate_up.size(-1) // 2
             )
         gate, up = gate_up.chunk(2, dim=-1)
-        return F.silu(gate.float()).to(gate_up.dtype) * up
+        return F.silu(gate.to(_ref_dtype(gate_up))).to(gate_up.dtype) * up
 
     @staticmethod
     def backward(ctx, dy: torch.Tensor):
@@ -37,12 +42,13 @@ class _SwiGLUFn(torch.autograd.Function):
             )
             return d.reshape(gate_up.shape)
         gate, up = gate_up.chunk(2, dim=-1)
-        g = gate.float()
+        ct = _ref_dtype(gate_up)
+        g = gate.to(ct)
         sig = torch.sigmoid(g)
         silu = g * sig
         dsilu = sig * (1 + g * (1 - sig))
-        dyf = dy.float()
-        dgate = (dyf * up.float() * dsilu).to(gate_up.dtype)
+        dyf = dy.to(ct)
+        dgate = (dyf * up.to(ct) * dsilu).to(gate_up.dtype)
         dup = (dyf * silu).to(gate_up.dtype)
         return torch.cat((dgate, dup), dim=-1)
 
