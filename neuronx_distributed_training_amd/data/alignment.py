@@ -118,6 +118,11 @@ class ModelAlignmentDataModule(BaseDataModule):
             )
         sft = self.align.get("sft", {})
         if sft.get("packing", False):
-            self.train_ds = ConcatDataset(samples, self.seq_length, eos)
+            # sft.packing_segment_mask: packed samples stay independent
+            # (per-document attention mask + first-token labels ignored)
+            self.train_ds = ConcatDataset(
+                samples, self.seq_length, eos,
+                segment_ids=bool(sft.get("packing_segment_mask", False)),
+            )
         else:
             self.train_ds = PaddedDataset(samples, self.seq_length, pad)

@@ -24,23 +24,39 @@ def pad_to(ids: List[int], length: int, value: int, left: bool = False):
 class ConcatDataset(Dataset):
     """Greedy packing: samples are concatenated (EOS-joined) until
     ``chunk_size`` tokens, overflow starts the next chunk
-    (reference ConcatDataset.py:24-77)."""
+    (reference ConcatDataset.py:24-77).
 
-    def __init__(self, dataset, chunk_size: int, eos_token_id: int = 2):
+    ``segment_ids=True`` additionally gives every item a ``segment_ids``
+    tensor for per-document attention masking (LlamaModel.forward): one id
+    per packed sample, counted from 0 in each chunk; a sample split across
+    chunks starts a new segment in each chunk; the pad tail gets an id of
+    its own. The label at each segment's first position then becomes
+    IGNORE_INDEX: it would be predicted from the previous document's last
+    token. The default output is unchanged."""
+
+    def __init__(self, dataset, chunk_size: int, eos_token_id: int = 2,
+                 segment_ids: bool = False):
         self.chunk_size = chunk_size
+        self.with_segment_ids = segment_ids
         chunks = []
         cur = {"input_ids": [], "labels": [], "attention_mask": []}
+        seg = []       # segment id per token of the current chunk
+        n_seg = 0      # segments in the current chunk so far
 
         def flush():
-            nonlocal cur
+            nonlocal cur, seg, n_seg
             if cur["input_ids"]:
                 n = len(cur["input_ids"])
                 if n < chunk_size:
                     cur["input_ids"] += [eos_token_id] * (chunk_size - n)
                     cur["labels"] += [IGNORE_INDEX] * (chunk_size - n)
                     cur["attention_mask"] += [0] * (chunk_size - n)
+                    seg += [n_seg] * (chunk_size - n)
+                if segment_ids:
+                    cur["segment_ids"] = seg
                 chunks.append(cur)
             cur = {"input_ids": [], "labels": [], "attention_mask": []}
+            seg, n_seg = [], 0
 
         for sample in dataset:
             ids = list(sample["input_ids"])
@@ -50,9 +66,13 @@ class ConcatDataset(Dataset):
                 pl = labels[start : start + chunk_size]
                 if len(cur["input_ids"]) + len(pi) > chunk_size:
                     flush()
+                if segment_ids:
+                    pl = [IGNORE_INDEX] + pl[1:]
                 cur["input_ids"] += pi
                 cur["labels"] += pl
                 cur["attention_mask"] += [1] * len(pi)
+                seg += [n_seg] * len(pi)
+                n_seg += 1
         flush()
         self.chunks = chunks
 
@@ -62,12 +82,15 @@ class ConcatDataset(Dataset):
     def __getitem__(self, i):
         c = self.chunks[i]
         labels = torch.tensor(c["labels"])
-        return {
+        item = {
             "input_ids": torch.tensor(c["input_ids"]),
             "labels": labels,
             "attention_mask": torch.tensor(c["attention_mask"]),
             "loss_mask": (labels != IGNORE_INDEX).float(),
         }
+        if self.with_segment_ids:
+            item["segment_ids"] = torch.tensor(c["segment_ids"])
+        return item
 
 
 class PaddedDataset(Dataset):

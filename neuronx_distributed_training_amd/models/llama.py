@@ -39,7 +39,7 @@ from ..parallel.mappings import (
     scatter_to_sequence_parallel_region,
 )
 from ..ops import flash_attn_func, swiglu
-from ..ops.flash_attn import mask_to_kv_range_tensors
+from ..ops.flash_attn import mask_to_kv_range_tensors, segment_bounds
 from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
 from ..ops.rmsnorm import RMSNorm
 
@@ -210,16 +210,22 @@ class LlamaAttention(nn.Module):
             k, v = kv.chunk(2, dim=-1)
         return q, k, v
 
-    def core_attention(self, q, k, v, kv_range=None):
+    def core_attention(self, q, k, v, kv_range=None, seg_bounds=None):
         """q/k/v: [b, h, s, d] bf16 → o [b, h, s, d]. The recompute unit for
         selective activation checkpointing (reference CoreAttention).
         Under context parallelism the flash kernel runs inside the CP ring
         (reference ring-attention dispatch, modeling_llama.py:482-489).
         kv_range: (kv_lo, kv_hi) int32 [b] visible key range of a padded
-        batch (LlamaModel.forward), None for dense batches."""
+        batch (LlamaModel.forward), None for dense batches.
+        seg_bounds: (q_start, k_end) int32 [b, s] of a packed batch
+        (ops.segment_bounds), None otherwise."""
         if ps.get_context_model_parallel_world_size() > 1:
             assert kv_range is None, \
                 "padding masks are not supported under context parallelism"
+            if seg_bounds is not None:
+                raise ValueError(
+                    "segment_ids are not supported under context parallelism"
+                )
             from ..ops.ring_attn import ring_flash_attn
 
             # the ring path has no sliding-window support yet: windowed
@@ -234,11 +240,12 @@ class LlamaAttention(nn.Module):
         return flash_attn_func(
             q, k, v, causal=True, scale=self.scale,
             window=getattr(self.cfg, "sliding_window", None),
-            kv_range=kv_range,
+            kv_range=kv_range, seg_bounds=seg_bounds,
         )
 
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
-                layer_idx: int = 0, pad_mask=None, kv_range=None):
+                layer_idx: int = 0, pad_mask=None, kv_range=None,
+                seg_bounds=None):
         # x: [s(, /tp if SP), b, h]
         s_dim, b = x.size(0), x.size(1)
         d = self.head_dim
@@ -274,10 +281,10 @@ class LlamaAttention(nn.Module):
                 window=getattr(self.cfg, "sliding_window", None),
             )
         elif self.cfg.activation_checkpoint == "selective" and self.training:
-            o = _ckpt(self.core_attention, q, k, v, kv_range,
+            o = _ckpt(self.core_attention, q, k, v, kv_range, seg_bounds,
                       use_reentrant=False)
         else:
-            o = self.core_attention(q, k, v, kv_range)
+            o = self.core_attention(q, k, v, kv_range, seg_bounds)
         o = o.permute(2, 0, 1, 3).reshape(s_full, b, self.n_heads_local * d)
         return self.o_proj(o)
 
@@ -311,10 +318,12 @@ class LlamaDecoderLayer(nn.Module):
         self.mlp = LlamaMLP(cfg, layer_idx)
 
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
-                layer_idx: int = 0, pad_mask=None, kv_range=None):
+                layer_idx: int = 0, pad_mask=None, kv_range=None,
+                seg_bounds=None):
         x = x + self.self_attn(self.input_layernorm(x), cos, sin, pos_offset,
                                cache=cache, layer_idx=layer_idx,
-                               pad_mask=pad_mask, kv_range=kv_range)
+                               pad_mask=pad_mask, kv_range=kv_range,
+                               seg_bounds=seg_bounds)
         x = x + self.mlp(self.post_attention_layernorm(x))
         return x
 
@@ -377,9 +386,47 @@ class LlamaModel(nn.Module):
             return attention_mask == 0, None
         return None, (lo, hi)
 
-    def forward(self, input_ids, kv_cache=None, attention_mask=None):
+    def _segments(self, segment_ids, input_ids, kv_cache):
+        """Packed batch: check that segmented flash attention can run and
+        derive its (q_start, k_end) bounds once per forward. No host sync.
+        There is no eager fallback: what the kernels lack is an error."""
+        if kv_cache is not None:
+            raise ValueError("segment_ids are not supported with a KV cache")
+        if ps.get_context_model_parallel_world_size() > 1:
+            raise ValueError(
+                "segment_ids are not supported under context parallelism"
+            )
+        if tuple(segment_ids.shape) != tuple(input_ids.shape):
+            raise ValueError(
+                f"segment_ids must have input_ids' shape "
+                f"{tuple(input_ids.shape)}, got {tuple(segment_ids.shape)}"
+            )
+        if input_ids.is_cuda and (
+            self.cfg.torch_dtype != torch.bfloat16
+            or self.cfg.head_dim not in (64, 128)
+        ):
+            raise ValueError(
+                "segmented flash attention on GPU needs bfloat16 and "
+                f"head_dim 64 or 128, got {self.cfg.torch_dtype} / "
+                f"head_dim {self.cfg.head_dim}"
+            )
+        return segment_bounds(segment_ids.to(input_ids.device))
+
+    def forward(self, input_ids, kv_cache=None, attention_mask=None,
+                segment_ids=None):
+        """segment_ids: optional int [b, s], non-decreasing along each row
+        (packed samples, data/packing.py). Each token then attends causally
+        inside its own segment only, through the segmented flash kernels.
+        attention_mask is not consulted: a pad tail must be its own
+        (trailing) segment. RoPE positions are NOT reset per document:
+        RoPE is relative (a score depends on i - j only), so isolation does
+        not need a reset."""
         # input_ids: [b, s(, /cp)] — CP split done by the trainer. With
         # kv_cache, input_ids are the NEW tokens only (decode path).
+        seg_bounds = None
+        if segment_ids is not None:
+            seg_bounds = self._segments(segment_ids, input_ids, kv_cache)
+            attention_mask = None
         if kv_cache is not None:
             assert not self.cfg.sequence_parallel, "kv cache requires SP off"
             pos_offset = kv_cache.seq_len
@@ -399,11 +446,11 @@ class LlamaModel(nn.Module):
             if full_ckpt:
                 x = _ckpt(layer, x, self.rope_cos, self.rope_sin, pos_offset,
                           use_reentrant=False, pad_mask=pad_mask,
-                          kv_range=kv_range)
+                          kv_range=kv_range, seg_bounds=seg_bounds)
             else:
                 x = layer(x, self.rope_cos, self.rope_sin, pos_offset,
                           cache=kv_cache, layer_idx=li, pad_mask=pad_mask,
-                          kv_range=kv_range)
+                          kv_range=kv_range, seg_bounds=seg_bounds)
         if kv_cache is not None:
             kv_cache.seq_len += input_ids.size(1)
         x = self.norm(x)
@@ -428,9 +475,12 @@ class LlamaForCausalLM(nn.Module):
     supports_kv_cache = True
 
     def forward(self, input_ids, labels=None, loss_mask=None, kv_cache=None,
-                attention_mask=None, loss_denominator=None):
+                attention_mask=None, loss_denominator=None,
+                segment_ids=None):
+        """segment_ids: see LlamaModel.forward (packed samples)."""
         hidden = self.model(input_ids, kv_cache=kv_cache,
-                            attention_mask=attention_mask)
+                            attention_mask=attention_mask,
+                            segment_ids=segment_ids)
         # under SP the model's output gather already provides the TP input
         # mapping (backward reduce-scatter); pre_mapped skips the copy so
         # the reduction isn't applied twice

@@ -78,7 +78,11 @@ def kernels_for(t: torch.Tensor):
 from .rmsnorm import rmsnorm  # noqa: E402
 from .rope import apply_rotary_pos_emb  # noqa: E402
 from .swiglu import swiglu  # noqa: E402
-from .flash_attn import flash_attn_func, mask_to_kv_range  # noqa: E402
+from .flash_attn import (  # noqa: E402
+    flash_attn_func,
+    mask_to_kv_range,
+    segment_bounds,
+)
 
 __all__ = [
     "have_extension",
@@ -89,4 +93,5 @@ __all__ = [
     "swiglu",
     "flash_attn_func",
     "mask_to_kv_range",
+    "segment_bounds",
 ]

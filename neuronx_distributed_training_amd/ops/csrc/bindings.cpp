@@ -40,6 +40,15 @@ void launch_flash_bwd_range(const void*, const void*, const void*,
                             void*, void*, int, int, int, int, int, int, bool,
                             float, int, const long*, const long*, const long*,
                             const long*, const int*, const int*, hipStream_t);
+void launch_flash_fwd_seg(const void*, const void*, const void*, void*, void*,
+                          int, int, int, int, int, float, int, const long*,
+                          const long*, const long*, const int*, const int*,
+                          hipStream_t);
+void launch_flash_bwd_seg(const void*, const void*, const void*, const void*,
+                          const void*, const void*, void*, void*, void*, int,
+                          int, int, int, int, float, int, const long*,
+                          const long*, const long*, const long*, const int*,
+                          const int*, hipStream_t);
 void launch_mfma_probe(const void*, const void*, void*, hipStream_t);
 void launch_mfma_probe32(const void*, const void*, void*, hipStream_t);
 void launch_flash_fwd_v3(const void*, const void*, const void*, void*, void*,
@@ -446,6 +455,86 @@ std::vector<torch::Tensor> flash_attn_bwd_range(
           dv_mem.permute({1, 2, 0, 3})};
 }
 
+static void check_seg_bound(const torch::Tensor& t, const torch::Tensor& q,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name,
+              " must be on the same GPU as q");
+  TORCH_CHECK(t.scalar_type() == torch::kInt, name, " must be int32");
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == q.size(0) &&
+                  t.size(1) == q.size(2),
+              name, " must have shape [B, S]");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_seg(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor q_start,
+    torch::Tensor k_end, double scale, long window) {
+  // causal flash_attn_fwd over packed sequences: query i of row b sees keys
+  // q_start[b,i] <= j <= i (block-diagonal mask). k_end[b,j] is one past
+  // the last query that sees key j. Values are trusted to be non-decreasing
+  // along each row with 0 <= q_start[b,i] <= i < k_end[b,i] <= S; the
+  // Python op derives them from segment ids.
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
+      D = (int)q.size(3);
+  int HKV = (int)k.size(1);
+  TORCH_CHECK(k.size(2) == S, "segmented attention needs S_q == S_kv");
+  check_seg_bound(q_start, q, "q_start");
+  check_seg_bound(k_end, q, "k_end");
+  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
+  auto o_mem = torch::empty({S, B, HQ, D}, q.options());
+  auto lse = torch::empty({B, HQ, S}, q.options().dtype(torch::kFloat32));
+  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
+  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
+  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
+  launch_flash_fwd_seg(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                       o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, S, D,
+                       (float)scale, (int)window, qs, ks, vs,
+                       q_start.data_ptr<int>(), k_end.data_ptr<int>(),
+                       cur_stream());
+  return {o_mem.permute({1, 2, 0, 3}), lse};
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_seg(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, torch::Tensor q_start,
+    torch::Tensor k_end, double scale, long window) {
+  if (dout.stride(3) != 1) dout = dout.contiguous();
+  check_bhsd(dout, "dout");
+  check_bhsd(q, "q");
+  lse = check_bwd_args(q, k, v, lse);
+  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
+      D = (int)q.size(3);
+  int HKV = (int)k.size(1);
+  TORCH_CHECK(k.size(2) == S, "segmented attention needs S_q == S_kv");
+  check_seg_bound(q_start, q, "q_start");
+  check_seg_bound(k_end, q, "k_end");
+  auto delta = attn_delta(dout, o);  // [B, HQ, S] f32, fused
+  // every q-block / key-block stores its whole slab, so torch::empty is safe
+  auto dq_mem = torch::empty({S, B, HQ, D}, q.options());
+  int group = HQ / HKV;
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto dk_part = torch::empty({group, S, B, HKV, D}, f32);
+  auto dv_part = torch::empty({group, S, B, HKV, D}, f32);
+  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
+  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
+  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
+  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
+  launch_flash_bwd_seg(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                       v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                       dq_mem.data_ptr(), dk_part.data_ptr(),
+                       dv_part.data_ptr(), B, HQ, HKV, S, D, (float)scale,
+                       (int)window, qs, ks, vs, ds, q_start.data_ptr<int>(),
+                       k_end.data_ptr<int>(), cur_stream());
+  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
+  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
+  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
+          dv_mem.permute({1, 2, 0, 3})};
+}
+
 torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
                        torch::Tensor tile_expert, torch::Tensor total_rows,
                        bool trans_b) {
@@ -594,6 +683,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("kv_lo"),
         pybind11::arg("kv_hi"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_seg", &flash_attn_fwd_seg, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("q_start"),
+        pybind11::arg("k_end"), pybind11::arg("scale"),
+        pybind11::arg("window") = 0);
+  m.def("flash_attn_bwd_seg", &flash_attn_bwd_seg, pybind11::arg("dout"),
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("q_start"),
+        pybind11::arg("k_end"), pybind11::arg("scale"),
+        pybind11::arg("window") = 0);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3, pybind11::arg("q"),

@@ -17,8 +17,15 @@
 // (their slabs are still written); query rows with no alive key get dQ = 0
 // and contribute nothing. RANGED=false compiles exactly as before and
 // never reads kv_lo / kv_hi.
+//
+// SEGMENTED (both kernels): packed sequences, block-diagonal causal mask
+// (S_q == S_kv), matching flash_fwd_dbuf_kernel<.., SEGMENTED>. The same
+// two pointers then carry per-token int32 [B, S] bounds: kv_lo = q_start
+// (first key query i may see) decides every mask bit; kv_hi = k_end (one
+// past the last query that sees key j) only bounds the dkv q-tile loop.
+// Both are non-decreasing along a row.
 // ============================ dK / dV ============================
-template <int D, bool CAUSAL, bool RANGED = false>
+template <int D, bool CAUSAL, bool RANGED = false, bool SEGMENTED = false>
 __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -31,8 +38,10 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     int SQ, int SKV, int Bb, int HQ, int HKV, float scale,
     int window, long sQs, long sQb, long sQh, long sKs, long sKb, long sKh,
     long sVs, long sVb, long sVh, long sDs, long sDb, long sDh,
-    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED only)
-    const int* __restrict__ kv_hi = nullptr) {
+    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED), or
+    const int* __restrict__ kv_hi = nullptr) {  // [B, S] (SEGMENTED)
+  static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
+  static_assert(!SEGMENTED || CAUSAL, "segments are causal");
   constexpr int BN = 256;  // keys per block
   // q tile 64 at 145 KB LDS = 1 block/CU. A BM=32 variant (79 KB, 2
   // blocks/CU) measured SLOWER (14.7 vs 12.0 ms) — the kernel is
@@ -121,8 +130,22 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
     if (CAUSAL && window > 0)
       nqb = min(nqb, (khi - 1 + window - coff + BM - 1) / BM);
     if (RANGED && klo >= khi) nqb = 0;
+    // SEGMENTED: no query at or past the end of the block's last key's
+    // segment sees any key of the block
+    const int* Sp = kv_lo + (long)b * SQ;  // q_start row (SEGMENTED only)
+    if constexpr (SEGMENTED)
+      nqb = min(nqb,
+                (kv_hi[(long)b * SQ + min(kbase + BN, SKV) - 1] + BM - 1) / BM);
+    // q_start of the tile's first query, fetched one tile ahead so the
+    // wave-skip test below never waits for the load
+    int qs_tile_next = 0;
+    if constexpr (SEGMENTED)
+      if (ib0 < nqb) qs_tile_next = Sp[ib0 * BM];
     for (int ib = ib0; ib < nqb; ++ib) {
       const int qbase = ib * BM;
+      const int qs_tile = qs_tile_next;
+      if constexpr (SEGMENTED)
+        if (ib + 1 < nqb) qs_tile_next = Sp[qbase + BM];
       {  // stage Q, dO row-major (16B) + transposed (paired b32)
         constexpr int KVECS = BM * D / 8;
         for (int t = threadIdx.x; t < KVECS; t += 512) {
@@ -166,7 +189,10 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
 
       // causal: skip waves whose keys are all above this q tile
       if ((!CAUSAL || wkey_min <= qbase + BM - 1 + coff) &&
-          (!RANGED || (krow_w < hi && krow_w + 32 > lo))) {
+          (!RANGED || (krow_w < hi && krow_w + 32 > lo)) &&
+          // SEGMENTED: the wave's keys all lie below the segment of the
+          // tile's first (hence every) query
+          (!SEGMENTED || krow_w + 32 > qs_tile)) {
         __bf16* pw = &pT_lds[wid * 32 * VP];
         __bf16* dw = &dsT_lds[wid * 32 * VP];
 #pragma unroll
@@ -188,12 +214,16 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
           const int qcol = qbase + nq * 16 + (lane & 15);
           const float lse = (qcol < SQ) ? Lp[qcol] : 1e30f;
           const float delta = (qcol < SQ) ? Dp[qcol] : 0.f;
+          int qs = 0;  // first key visible to qcol
+          if constexpr (SEGMENTED) qs = (qcol < SQ) ? Sp[qcol] : 0;
           // interior fast path (the fwd kernel's full_tile analog): every
           // (q, key) of this 16-col x 32-key patch in bounds and causally
           // alive — skip the 3 compare/selects per element (VALU-bound
           // kernel)
           const bool full_patch =
               (!RANGED || (krow_w >= lo && krow_w + 31 < hi)) &&
+              // lane 15 holds the patch's last query (largest q_start)
+              (!SEGMENTED || krow_w >= __builtin_amdgcn_readlane(qs, 15)) &&
               (qbase + nq * 16 + 15 < SQ) && (krow_w + 31 < SKV) &&
               (!CAUSAL || (qbase + nq * 16 + coff >= krow_w + 31)) &&
               (window <= 0 ||
@@ -221,6 +251,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
                 if (CAUSAL && window > 0)
                   dead |= (qcol + coff >= krow + window);
                 if constexpr (RANGED) dead |= (krow < lo) || (krow >= hi);
+                if constexpr (SEGMENTED) dead |= (krow < qs);
                 const float p = dead ? 0.f : __expf(st[sb][r] - lse);
                 const float ds = p * (dpt[sb][r] - delta) * scale;
                 const int lrow = sb * 16 + (lane >> 4) * 4 + r;
@@ -273,7 +304,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
 // ============================ dQ ============================
 // NSB: 16-row sub-blocks per wave (see flash_fwd_kernel) — NSB=1 keeps
 // the chip full at TP=8's HQ_local=4
-template <int D, bool CAUSAL, int NSB, bool RANGED = false>
+template <int D, bool CAUSAL, int NSB, bool RANGED = false,
+          bool SEGMENTED = false>
 __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -282,8 +314,10 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     int SQ, int SKV, int Bb, int HQ, int HKV, float scale, int window,
     long sQs, long sQb, long sQh, long sKs, long sKb, long sKh, long sVs,
     long sVb, long sVh, long sDs, long sDb, long sDh,
-    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED only)
-    const int* __restrict__ kv_hi = nullptr) {
+    const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED), or
+    const int* __restrict__ kv_hi = nullptr) {  // [B, S] (SEGMENTED)
+  static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
+  static_assert(!SEGMENTED || CAUSAL, "segments are causal");
   constexpr int BM = NSB * 128, BN = 64;  // BN=32 (2 blk/CU) was slower
   const int coff = SKV - SQ;  // bottom-right causal alignment
   constexpr int KP = D + 8;
@@ -324,6 +358,19 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
   constexpr int DK = D / 32;
   bf16x8_t qfrag[NSB][DK], dofrag[NSB][DK];
   float lse[NSB][4], delta[NSB][4];
+  // SEGMENTED: first visible key of each of the lane's 4*NSB rows, of the
+  // wave's last row (full_patch) and of its first row (tile skip)
+  int qs[NSB][4], qs_last = 0, qs_wave = 0;
+  if constexpr (SEGMENTED) {
+    const int* Sp = kv_lo + (long)b * SQ;
+    qs_wave = Sp[min(qrow_w, SQ - 1)];
+    qs_last = Sp[min(qrow_w + NSB * 16 - 1, SQ - 1)];
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr)
+        qs[sb][rr] = Sp[min(qrow_w + sb * 16 + (lane >> 4) * 4 + rr, SQ - 1)];
+  }
 #pragma unroll
   for (int sb = 0; sb < NSB; ++sb) {
     const int r = qrow_w + sb * 16 + (lane & 15);
@@ -373,6 +420,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
   // tiles wholly below lo are skipped; jb0 >= nkb leaves the loop empty
   // and the zero dQ accumulators are stored
   if constexpr (RANGED) jb0 = max(jb0, lo / BN);
+  // SEGMENTED: no row of the tile sees a key below its first row's segment
+  if constexpr (SEGMENTED) jb0 = max(jb0, kv_lo[(long)b * SQ + q0] / BN);
   const int wrow_max = qrow_w + NSB * 16 - 1;
 
   auto stage_kv = [&](int jb, int buf) {
@@ -419,7 +468,8 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     // barrier that ended tile jb-1) while this tile's MFMAs run
     if (jb + 1 < nkb) stage_kv(jb + 1, cur ^ 1);
 
-    if (!CAUSAL || kbase <= wrow_max + coff) {
+    if ((!CAUSAL || kbase <= wrow_max + coff) &&
+        (!SEGMENTED || kbase + BN > qs_wave)) {
       __bf16* dsw = &ds_lds[wid * NSB * 16 * VP];
 #pragma unroll
       for (int nk = 0; nk < BN / 16; ++nk) {
@@ -447,6 +497,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
         const bool full_patch =
             (!RANGED ||
              (kbase + nk * 16 >= lo && kbase + nk * 16 + 15 < hi)) &&
+            (!SEGMENTED || kbase + nk * 16 >= qs_last) &&
             (kbase + nk * 16 + 15 < SKV) &&
             (!CAUSAL || (kbase + nk * 16 + 15 <= qrow_w + coff)) &&
             (window <= 0 || (kbase + nk * 16 > qrow_w + 31 + coff - window));
@@ -471,6 +522,7 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
               if (CAUSAL && window > 0)
                 dead |= (kcol <= qrow + coff - window);
               if constexpr (RANGED) dead |= (kcol < lo) || (kcol >= hi);
+              if constexpr (SEGMENTED) dead |= (kcol < qs[sb][r]);
               const float p = dead ? 0.f : __expf(st[sb][r] - lse[sb][r]);
               const float ds = p * (dpt[sb][r] - delta[sb][r]) * scale;
               dsw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 +
@@ -663,6 +715,52 @@ void launch_flash_bwd_range(const void* dout, const void* q, const void* k,
   } else if (D == 64) {
     if (causal) CASE(64, true); else CASE(64, false);
   }
+#undef CASE
+}
+
+// same grids as launch_flash_bwd, SEGMENTED instantiations (causal,
+// S_q == S_kv == S): q_start / k_end are device int32 [B, S], non-decreasing
+// along each row, with 0 <= q_start[b,i] <= i < k_end[b,i] <= S
+void launch_flash_bwd_seg(const void* dout, const void* q, const void* k,
+                      const void* v, const void* lse, const void* delta,
+                      void* dq, void* dk, void* dv, int B, int HQ, int HKV,
+                      int S, int D, float scale, int window,
+                      const long* qstr, const long* kstr, const long* vstr,
+                      const long* dostr, const int* q_start, const int* k_end,
+                      hipStream_t stream) {
+  dim3 blk(512);
+  dim3 gkv((S + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
+  const bool small = ((long)((S + 255) / 256) * B * HQ) < 512;
+  const int bm = small ? 128 : 256;
+  dim3 gq((S + bm - 1) / bm, B * HQ);
+#define CASE(DD)                                                              \
+  do {                                                                        \
+    flash_bwd_dkv_kernel<DD, true, false, true><<<gkv, blk, 0, stream>>>(     \
+        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
+        (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, S,   \
+        S, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],     \
+        kstr[1],                                                              \
+        kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],     \
+        q_start, k_end);                                                      \
+    if (small)                                                                \
+      flash_bwd_dq_kernel<DD, true, 1, false, true>                           \
+          <<<gq, blk, 0, stream>>>(                                           \
+          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
+          (const float*)lse, (const float*)delta, (bf16*)dq, S, S, B, HQ,     \
+          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
+          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
+          q_start, k_end);                                                    \
+    else                                                                      \
+      flash_bwd_dq_kernel<DD, true, 2, false, true>                           \
+          <<<gq, blk, 0, stream>>>(                                           \
+          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
+          (const float*)lse, (const float*)delta, (bf16*)dq, S, S, B, HQ,     \
+          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
+          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
+          q_start, k_end);                                                    \
+  } while (0)
+  if (D == 128) CASE(128);
+  else if (D == 64) CASE(64);
 #undef CASE
 }
 }

@@ -14,7 +14,25 @@
 // tokens per row). Key-side only; a query row with no alive key stores
 // O = 0 and a finite LSE. The dense instantiations (RANGED=false) compile
 // exactly as before and never read kv_lo / kv_hi.
-template <int D, bool CAUSAL, int NSB, bool RANGED = false>
+//
+// SEGMENTED: packed sequences, block-diagonal causal mask (S_q == S_kv).
+// The same two pointers then carry per-token int32 [B, S] bounds instead:
+// kv_lo = q_start (first key query i may see = start of its segment) and
+// kv_hi = k_end (unused here; the dK/dV kernel bounds its q loop with it).
+// q_start is non-decreasing along a row, so a tile's bounds come from its
+// first / last row. Every query sees itself: no empty rows.
+
+// LDS home of the q_start values of a block's N query rows. The buffer
+// exists only in kernels that call this (the SEGMENTED ones), so the other
+// instantiations keep their LDS size.
+template <int N>
+__device__ __forceinline__ int* seg_bounds_lds() {
+  __shared__ __attribute__((aligned(16))) int buf[N];
+  return buf;
+}
+
+template <int D, bool CAUSAL, int NSB, bool RANGED = false,
+          bool SEGMENTED = false>
 __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, bf16* __restrict__ O,
@@ -24,8 +42,10 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     long sQs, long sQb, long sQh,   // Q element strides (seq, batch, head)
     long sKs, long sKb, long sKh,   // K strides
     long sVs, long sVb, long sVh,   // V strides
-    const int* __restrict__ kv_lo = nullptr,   // [B] int32 (RANGED only)
-    const int* __restrict__ kv_hi = nullptr) {
+    const int* __restrict__ kv_lo = nullptr,   // [B] int32 (RANGED), or
+    const int* __restrict__ kv_hi = nullptr) { // [B, S] (SEGMENTED)
+  static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
+  static_assert(!SEGMENTED || CAUSAL, "segments are causal");
   constexpr int BM = NSB * 128, BN = 64;
   constexpr int KP = D + 8;
   constexpr int VP = BN + 8;
@@ -75,6 +95,26 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     }
   }
 
+  // SEGMENTED: first visible key of the last row of each sub-block
+  // (full_tile) and of the wave's first row (tiles wholly below it are
+  // skipped by the whole wave), wave-uniform. The per-row bounds of the
+  // block's BM rows sit in LDS and are read by masked tiles only: held in
+  // 4*NSB VGPRs per lane they pushed the D=128 / BM=256 instantiation to
+  // its 256-VGPR budget and cost the one-segment forward 11% over dense.
+  int qs_last[NSB], qs_wave = 0;
+  int* qs_lds = nullptr;
+  if constexpr (SEGMENTED) {
+    const int* Sp = kv_lo + (long)b * SQ;
+    qs_wave = Sp[min(qrow_w, SQ - 1)];
+#pragma unroll
+    for (int sb = 0; sb < NSB; ++sb)
+      qs_last[sb] = Sp[min(qrow_w + sb * 16 + 15, SQ - 1)];
+    qs_lds = seg_bounds_lds<BM>();
+    // visible after the barrier that follows the first K/V stage
+    if (threadIdx.x < BM)
+      qs_lds[threadIdx.x] = Sp[min(q0 + (int)threadIdx.x, SQ - 1)];
+  }
+
   float m_i[NSB][4], l_i[NSB][4];
   float alpha_s[NSB][4];
   // all-ones B fragment: one MFMA per 32-key chunk computes the P row-sums
@@ -104,6 +144,8 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
   // tiles wholly below lo are skipped; jb0 >= nkb (no alive tile) leaves
   // the loop empty and the epilogue stores O = 0 / LSE = -1e30
   if constexpr (RANGED) jb0 = max(jb0, lo / BN);
+  // SEGMENTED: no row of the tile sees a key below its first row's segment
+  if constexpr (SEGMENTED) jb0 = max(jb0, kv_lo[(long)b * SQ + q0] / BN);
   const int wrow_max = qrow_w + NSB * 16 - 1;
 
   // T5 static form: the younger dispatch half gets priority so it is not
@@ -180,7 +222,8 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     const int cur = jb & 1;
     if (jb + 1 < nkb) issue_loads((jb + 1) * BN);
 
-    if (!CAUSAL || kbase <= wrow_max + coff) {
+    if ((!CAUSAL || kbase <= wrow_max + coff) &&
+        (!SEGMENTED || kbase + BN > qs_wave)) {
       // ---- S = Q K^T for both sub-blocks (B-frags loaded once) ----
       f32x4_t sacc[NSB][4];
 #pragma unroll
@@ -204,6 +247,7 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
         // interior tiles (every key visible to every row) skip the mask
         const bool full_tile =
             (!RANGED || (kbase >= lo && kbase + BN <= hi)) &&
+            (!SEGMENTED || kbase >= qs_last[sb]) &&
             (kbase + BN <= SKV) &&
             (!CAUSAL || (kbase + BN - 1 <= qrow_w + sb * 16 + coff)) &&
             (window <= 0 || kbase >= qrow_w + sb * 16 + coff + 15 - window + 1);
@@ -220,6 +264,10 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
             }
           }
         } else {
+          int qs[4] = {0, 0, 0, 0};  // first visible key of the lane's rows
+          if constexpr (SEGMENTED)
+            *(int4*)qs = *(const int4*)&qs_lds[(wid * NSB + sb) * 16 +
+                                               (lane >> 4) * 4];
 #pragma unroll
           for (int nk = 0; nk < 4; ++nk) {
             const int kcol = kbase + nk * 16 + (lane & 15);
@@ -230,7 +278,15 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
               bool dead = (kcol >= SKV) || (CAUSAL && kcol > qrow + coff);
               if (CAUSAL && window > 0) dead |= (kcol <= qrow + coff - window);
               if constexpr (RANGED) dead |= (kcol < lo) || (kcol >= hi);
-              s = dead ? -1e30f : s;
+              if constexpr (SEGMENTED) dead |= (kcol < qs[r]);
+              // SEGMENTED: a row whose segment starts above the first tile
+              // its wave visits sees fully dead tiles while m_i is still
+              // -1e30, and exp(-1e30 - m_i) would be 1. Dead scores are
+              // -inf there instead: m_i stays finite (tile_max starts at
+              // -1e30), so p = exp(-inf) = 0 exactly with no select in the
+              // exp loop, which runs on every tile (a select there cost
+              // the one-segment forward 17% over dense).
+              s = dead ? (SEGMENTED ? -__builtin_inff() : -1e30f) : s;
               sv[nk][r] = s;
               tile_max[r] = fmaxf(tile_max[r], s);
             }
@@ -271,7 +327,9 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
             float p = __expf(sv[nk][r] - m_i[sb][r]);
             // a row with no alive key yet still has m_i = -1e30, so its
             // dead entries would get exp(0) = 1 (dense causal rows always
-            // see themselves; rows below lo do not) — force them to 0
+            // see themselves; rows below lo do not) — force them to 0.
+            // (SEGMENTED meets the same trap and avoids it with s = -inf
+            // on dead entries, see above.)
             if constexpr (RANGED) p = (sv[nk][r] < -1e29f) ? 0.f : p;
             pw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 + (lane & 15)] =
                 (__bf16)p;
@@ -406,6 +464,40 @@ void launch_flash_fwd_range(const void* q, const void* k, const void* v, void* o
   } else if (D == 64) {
     if (causal) CASE(64, true); else CASE(64, false);
   }
+#undef CASE
+}
+
+// SEGMENTED instantiations (causal, S_q == S_kv == S): q_start / k_end are
+// device int32 [B, S], non-decreasing along each row, with
+// 0 <= q_start[b,i] <= i < k_end[b,i] <= S. Same tiling rule as above.
+void launch_flash_fwd_seg(const void* q, const void* k, const void* v, void* o,
+                      void* lse, int B, int HQ, int HKV, int S, int D,
+                      float scale, int window, const long* qstr,
+                      const long* kstr, const long* vstr, const int* q_start,
+                      const int* k_end, hipStream_t stream) {
+  const bool small = ((long)((S + 255) / 256) * B * HQ) < 512;
+  const int bm = small ? 128 : 256;
+  dim3 grid((S + bm - 1) / bm, B * HQ);
+  dim3 blk(512);
+#define CASE(DD)                                                              \
+  do {                                                                        \
+    if (small)                                                                \
+      flash_fwd_dbuf_kernel<DD, true, 1, false, true>                         \
+          <<<grid, blk, 0, stream>>>(                                         \
+          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
+          (float*)lse, S, S, B, HQ, HKV, scale, window, qstr[0], qstr[1],     \
+          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
+          q_start, k_end);                                                    \
+    else                                                                      \
+      flash_fwd_dbuf_kernel<DD, true, 2, false, true>                         \
+          <<<grid, blk, 0, stream>>>(                                         \
+          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
+          (float*)lse, S, S, B, HQ, HKV, scale, window, qstr[0], qstr[1],     \
+          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
+          q_start, k_end);                                                    \
+  } while (0)
+  if (D == 128) CASE(128);
+  else if (D == 64) CASE(64);
 #undef CASE
 }
 }

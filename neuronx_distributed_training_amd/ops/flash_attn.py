@@ -17,6 +17,14 @@ key range ``[kv_lo[b], kv_hi[b])`` on top of the causal / window mask
 (key-side only). A query row with no alive key gets O = 0, dQ = 0 and a
 finite LSE; keys outside the range get dK = dV = 0. Ranged calls always run
 the v2 kernels.
+
+Packed sequences: ``segment_ids`` [B, S] (non-decreasing along each row)
+makes the causal mask block-diagonal: query i sees key j iff they share a
+segment id, ``j <= i`` and j is inside the sliding window if there is one.
+Every query sees itself, so there are no empty rows. The kernels take the
+two derived arrays of :func:`segment_bounds`, not the ids. Segmented calls
+need ``S_q == S_kv`` and ``causal=True``, exclude ``kv_range`` and always
+run the v2 kernels.
 """
 
 from __future__ import annotations
@@ -99,8 +107,37 @@ def _norm_kv_range(kv_range, b, skv, device):
     return lo.contiguous(), hi.contiguous()
 
 
-def _make_mask(sq, sk, causal, window, device, kv_lo=None, kv_hi=None):
-    """True = dead. [sq, sk], or [b, 1, sq, sk] with a key range."""
+def segment_bounds(segment_ids):
+    """[B, S] segment ids (non-decreasing along each row) -> int32 [B, S]
+    ``(q_start, k_end)``: ``q_start[b, i]`` is the first position of token
+    i's segment (the first key query i may see), ``k_end[b, j]`` one past
+    its last position (one past the last query that may see key j). Both
+    are non-decreasing. Runs on the ids' device without a host sync."""
+    if segment_ids.dim() != 2:
+        raise ValueError(
+            f"segment_ids must be [B, S], got {tuple(segment_ids.shape)}"
+        )
+    b, s = segment_ids.shape
+    pos = torch.arange(s, device=segment_ids.device, dtype=torch.int32)
+    pos = pos.expand(b, s)
+    new = torch.ones(b, s, dtype=torch.bool, device=segment_ids.device)
+    new[:, 1:] = segment_ids[:, 1:] != segment_ids[:, :-1]
+    # start: running max of "position if a segment starts here"
+    q_start = torch.cummax(torch.where(new, pos, torch.zeros_like(pos)),
+                           dim=1).values
+    # end: running min from the right of "position + 1 if one ends here"
+    last = torch.ones_like(new)
+    last[:, :-1] = new[:, 1:]
+    end = torch.where(last, pos + 1, torch.full_like(pos, s))
+    k_end = torch.cummin(end.flip(1), dim=1).values.flip(1)
+    return (q_start.to(torch.int32).contiguous(),
+            k_end.to(torch.int32).contiguous())
+
+
+def _make_mask(sq, sk, causal, window, device, kv_lo=None, kv_hi=None,
+               q_start=None):
+    """True = dead. [sq, sk], or [b, 1, sq, sk] with a key range or
+    segment starts."""
     # S_q != S_kv: bottom-right alignment (query i sees keys
     # j <= i + sk - sq) — matches the HIP kernel's decode convention
     mask = torch.zeros(sq, sk, dtype=torch.bool, device=device)
@@ -117,6 +154,12 @@ def _make_mask(sq, sk, causal, window, device, kv_lo=None, kv_hi=None):
         j = torch.arange(sk, device=device)
         out = (j[None, :] < kv_lo[:, None]) | (j[None, :] >= kv_hi[:, None])
         mask = mask[None, None] | out[:, None, None, :]
+    if q_start is not None:
+        # with the causal mask, "same segment" is "key not below the start
+        # of the query's segment"
+        j = torch.arange(sk, device=device)
+        out = j[None, None, :] < q_start[:, :, None]         # [b, sq, sk]
+        mask = mask[None, None] | out[:, None]
     return mask
 
 
@@ -134,7 +177,8 @@ def _ranged_softmax(s, mask):
     return p, lse.squeeze(-1)
 
 
-def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None):
+def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None,
+                 q_start=None):
     hq, hkv = q.size(1), k.size(1)
     if hq != hkv:
         k = k.repeat_interleave(hq // hkv, dim=1)
@@ -142,7 +186,7 @@ def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None):
     qf, kf, vf = q.float(), k.float(), v.float()
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
     mask = _make_mask(q.size(-2), k.size(-2), causal, window, q.device,
-                      kv_lo, kv_hi)
+                      kv_lo, kv_hi, q_start)
     if kv_lo is not None:
         p, lse = _ranged_softmax(s, mask)
     else:
@@ -156,10 +200,16 @@ def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None):
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, causal: bool, scale: float, window: int = 0,
-                kv_lo=None, kv_hi=None):
+                kv_lo=None, kv_hi=None, q_start=None, k_end=None):
         kern = kernels_for(q)
         ranged = kv_lo is not None
-        if kern is not None and ranged:
+        segmented = q_start is not None
+        if kern is not None and segmented:
+            # segmented calls always use the v2 kernels too
+            o, lse = kern.flash_attn_fwd_seg(
+                q, k, v, q_start, k_end, scale, window
+            )
+        elif kern is not None and ranged:
             # ranged calls always use the v2 kernels (like S_q != S_kv)
             o, lse = kern.flash_attn_fwd_range(
                 q, k, v, kv_lo, kv_hi, causal, scale, window
@@ -171,12 +221,15 @@ class _FlashAttnFn(torch.autograd.Function):
             )
         else:
             o, lse = _cpu_ref_fwd(q, k, v, causal, scale, window,
-                                  kv_lo, kv_hi)
-        if ranged:
+                                  kv_lo, kv_hi, q_start)
+        if segmented:
+            ctx.save_for_backward(q, k, v, o, lse, q_start, k_end)
+        elif ranged:
             ctx.save_for_backward(q, k, v, o, lse, kv_lo, kv_hi)
         else:
             ctx.save_for_backward(q, k, v, o, lse)
         ctx.ranged = ranged
+        ctx.segmented = segmented
         ctx.causal = causal
         ctx.scale = scale
         ctx.window = window
@@ -184,23 +237,31 @@ class _FlashAttnFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, do):
-        kv_lo = kv_hi = None
-        if ctx.ranged:
+        kv_lo = kv_hi = q_start = k_end = None
+        none7 = (None,) * 7
+        if ctx.segmented:
+            q, k, v, o, lse, q_start, k_end = ctx.saved_tensors
+        elif ctx.ranged:
             q, k, v, o, lse, kv_lo, kv_hi = ctx.saved_tensors
         else:
             q, k, v, o, lse = ctx.saved_tensors
         kern = kernels_for(q)
+        if kern is not None and ctx.segmented:
+            dq, dk, dv = kern.flash_attn_bwd_seg(
+                do, q, k, v, o, lse, q_start, k_end, ctx.scale, ctx.window
+            )
+            return (dq, dk, dv) + none7
         if kern is not None and ctx.ranged:
             dq, dk, dv = kern.flash_attn_bwd_range(
                 do, q, k, v, o, lse, kv_lo, kv_hi, ctx.causal, ctx.scale,
                 ctx.window,
             )
-            return dq, dk, dv, None, None, None, None, None
+            return (dq, dk, dv) + none7
         if kern is not None:
             dq, dk, dv = _bwd_fn(kern, q.size(2), k.size(2))(
                 do, q, k, v, o, lse, ctx.causal, ctx.scale, ctx.window
             )
-            return dq, dk, dv, None, None, None, None, None
+            return (dq, dk, dv) + none7
         # CPU reference backward (fp32, explicit)
         hq, hkv = q.size(1), k.size(1)
         g = hq // hkv
@@ -209,7 +270,7 @@ class _FlashAttnFn(torch.autograd.Function):
         qf, dof = q.float(), do.float()
         s = torch.matmul(qf, kx.transpose(-1, -2)) * ctx.scale
         mask = _make_mask(q.size(-2), k.size(-2), ctx.causal, ctx.window,
-                          q.device, kv_lo, kv_hi)
+                          q.device, kv_lo, kv_hi, q_start)
         if ctx.ranged:
             p, _ = _ranged_softmax(s, mask)
         else:
@@ -224,8 +285,7 @@ class _FlashAttnFn(torch.autograd.Function):
         if g > 1:
             dk = dk.reshape(dk.size(0), hkv, g, dk.size(-2), dk.size(-1)).sum(2)
             dv = dv.reshape(dv.size(0), hkv, g, dv.size(-2), dv.size(-1)).sum(2)
-        return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype), None, None,
-                None, None, None)
+        return (dq.to(q.dtype), dk.to(k.dtype), dv.to(v.dtype)) + none7
 
 
 def flash_attn_func(
@@ -236,15 +296,50 @@ def flash_attn_func(
     scale: float | None = None,
     window: int | None = None,
     kv_range=None,
+    segment_ids=None,
+    seg_bounds=None,
 ) -> torch.Tensor:
     """window: sliding-window size (attend to the last `window` keys);
     None/0 disables (Mixtral sliding_window parity).
 
     kv_range: optional pair ``(kv_lo, kv_hi)`` of int tensors [B]; batch
     row b only sees keys ``kv_lo[b] <= j < kv_hi[b]`` (see
-    :func:`mask_to_kv_range`). None = dense attention."""
+    :func:`mask_to_kv_range`). None = dense attention.
+
+    segment_ids: optional int tensor [B, S], non-decreasing along each row
+    (packed sequences). Query i sees key j iff both carry the same id,
+    ``j <= i`` and j is inside the window; a pad tail is its own trailing
+    segment. Needs ``causal=True`` and ``S_q == S_kv``; excludes
+    ``kv_range``. ``seg_bounds`` passes the precomputed result of
+    :func:`segment_bounds` instead (a model computes it once per forward)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.size(-1))
+    if segment_ids is not None or seg_bounds is not None:
+        if segment_ids is not None and seg_bounds is not None:
+            raise ValueError("give segment_ids or seg_bounds, not both")
+        if kv_range is not None:
+            raise ValueError("segment_ids and kv_range are mutually exclusive")
+        if not causal:
+            raise ValueError("segment_ids needs causal=True")
+        if q.size(2) != k.size(2):
+            raise ValueError(
+                f"segment_ids needs S_q == S_kv, got {q.size(2)} / {k.size(2)}"
+            )
+        if seg_bounds is None:
+            seg_bounds = segment_bounds(
+                torch.as_tensor(segment_ids, device=q.device)
+            )
+        q_start, k_end = seg_bounds
+        want = (q.size(0), q.size(2))
+        if tuple(q_start.shape) != want or tuple(k_end.shape) != want:
+            raise ValueError(
+                f"segment_ids must have shape {list(want)}, got "
+                f"{tuple(q_start.shape)}"
+            )
+        return _FlashAttnFn.apply(
+            q, k, v, True, scale, int(window or 0), None, None,
+            q_start, k_end,
+        )
     if kv_range is None:
         return _FlashAttnFn.apply(q, k, v, causal, scale, int(window or 0))
     kv_lo, kv_hi = _norm_kv_range(kv_range, q.size(0), k.size(2), q.device)

@@ -119,6 +119,9 @@ class BaseModelModule:
             kw["attention_mask"] = batch["attention_mask"]
         if batch.get("loss_denominator") is not None:
             kw["loss_denominator"] = batch["loss_denominator"]
+        if batch.get("segment_ids") is not None:
+            # packed samples (sft.packing_segment_mask): per-document mask
+            kw["segment_ids"] = batch["segment_ids"]
         return self.model(
             batch["input_ids"],
             labels=batch.get("labels", batch["input_ids"]),
