@@ -154,25 +154,58 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
   return y_mem.permute({1, 2, 0, 3});
 }
 
+static void check_adamw_f32(const torch::Tensor& t, const torch::Tensor& p,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == p.device(), "adamw: ", name,
+              " must be on the same GPU as p");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, "adamw: ", name,
+              " must be fp32");
+  TORCH_CHECK(t.is_contiguous(), "adamw: ", name, " must be contiguous");
+  TORCH_CHECK(t.numel() == p.numel(), "adamw: ", name,
+              " must have p's numel");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "adamw: ",
+              name, " must be 16-byte aligned");
+}
+
 void adamw_step(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 torch::Tensor v, torch::Tensor wd_mask, double lr, double b1,
                 double b2, double eps, double wd, long step,
                 c10::optional<torch::Tensor> grad_scale,
                 c10::optional<torch::Tensor> p_bf16) {
-  CHECK_IN(p);
-  CHECK_IN(g);
+  // The kernel indexes all five arrays as dense [n] with no strides and
+  // moves p/g/m/v as float4 and p_bf16 as int2, so everything it reads is
+  // checked here, before the launch.
+  check_adamw_f32(p, p, "p");
+  check_adamw_f32(g, p, "g");
+  check_adamw_f32(m, p, "m");
+  check_adamw_f32(v, p, "v");
+  TORCH_CHECK(wd_mask.is_cuda() && wd_mask.device() == p.device(),
+              "adamw: wd_mask must be on the same GPU as p");
+  TORCH_CHECK(wd_mask.scalar_type() == torch::kBool,
+              "adamw: wd_mask must be bool");
+  TORCH_CHECK(wd_mask.is_contiguous() && wd_mask.numel() == p.numel(),
+              "adamw: wd_mask must be contiguous with p's numel");
+  // bc1 = 1 - b1^step and bc2 = 1 - b2^step are both zero at step 0
+  TORCH_CHECK(step >= 1, "adamw: step must be >= 1");
   void* gs = nullptr;
   if (grad_scale.has_value()) {
     TORCH_CHECK(grad_scale->scalar_type() == torch::kFloat32 &&
-                    grad_scale->is_cuda(),
+                    grad_scale->is_cuda() &&
+                    grad_scale->device() == p.device(),
                 "grad_scale must be a device fp32 scalar");
+    TORCH_CHECK(grad_scale->numel() == 1,
+                "grad_scale must have exactly one element");
     gs = grad_scale->data_ptr();
   }
   void* pb = nullptr;
   if (p_bf16.has_value()) {
+    TORCH_CHECK(p_bf16->is_cuda() && p_bf16->device() == p.device(),
+                "adamw: p_bf16 must be on the same GPU as p");
     TORCH_CHECK(p_bf16->scalar_type() == torch::kBFloat16 &&
                     p_bf16->is_contiguous() && p_bf16->numel() == p.numel(),
                 "p_bf16 must be contiguous bf16 of the same numel");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p_bf16->data_ptr()) % 8 == 0,
+                "adamw: p_bf16 must be 8-byte aligned");
     pb = p_bf16->data_ptr();
   }
   launch_adamw(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
