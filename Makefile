@@ -1,7 +1,7 @@
 # Convenience targets (see docs/general/installation_guide.md)
 PY ?= python
 
-.PHONY: build test test-gpu bench smoke parity bench-attn bench-decode family-smoke clean
+.PHONY: build test test-gpu bench smoke parity bench-attn bench-dkv bench-decode family-smoke clean
 
 build:
 	PYTORCH_ROCM_ARCH=gfx950 $(PY) setup.py build_ext --inplace
@@ -24,6 +24,9 @@ parity:
 
 bench-attn:
 	$(PY) tools/bench_attn_kernels.py --iters 10
+
+bench-dkv:
+	$(PY) tools/bench_dkv_ab.py --rounds 5
 
 bench-decode:
 	$(PY) tools/bench_decode.py

@@ -28,7 +28,8 @@ void launch_flash_fwd_dbuf(const void*, const void*, const void*, void*,
 void launch_flash_bwd(const void*, const void*, const void*, const void*,
                       const void*, const void*, void*, void*, void*, int, int,
                       int, int, int, int, bool, float, int, const long*,
-                      const long*, const long*, const long*, hipStream_t);
+                      const long*, const long*, const long*, bool,
+                      hipStream_t);
 void launch_attn_delta(const void*, const void*, void*, int, int, int, int,
                        const long*, const long*, hipStream_t);
 void launch_flash_fwd_range(const void*, const void*, const void*, void*,
@@ -39,7 +40,8 @@ void launch_flash_bwd_range(const void*, const void*, const void*,
                             const void*, const void*, const void*, void*,
                             void*, void*, int, int, int, int, int, int, bool,
                             float, int, const long*, const long*, const long*,
-                            const long*, const int*, const int*, hipStream_t);
+                            const long*, const int*, const int*, bool,
+                            hipStream_t);
 void launch_flash_fwd_seg(const void*, const void*, const void*, void*, void*,
                           int, int, int, int, int, float, int, const long*,
                           const long*, const long*, const int*, const int*,
@@ -48,7 +50,7 @@ void launch_flash_bwd_seg(const void*, const void*, const void*, const void*,
                           const void*, const void*, void*, void*, void*, int,
                           int, int, int, int, float, int, const long*,
                           const long*, const long*, const long*, const int*,
-                          const int*, hipStream_t);
+                          const int*, bool, hipStream_t);
 void launch_mfma_probe(const void*, const void*, void*, hipStream_t);
 void launch_mfma_probe32(const void*, const void*, void*, hipStream_t);
 void launch_flash_fwd_v3(const void*, const void*, const void*, void*, void*,
@@ -373,42 +375,6 @@ std::vector<torch::Tensor> flash_attn_fwd_sbuf(torch::Tensor q,
   return {o_mem.permute({1, 2, 0, 3}), lse};
 }
 
-std::vector<torch::Tensor> flash_attn_bwd(torch::Tensor dout, torch::Tensor q,
-                                          torch::Tensor k, torch::Tensor v,
-                                          torch::Tensor o, torch::Tensor lse,
-                                          bool causal, double scale,
-                                          long window) {
-  if (dout.stride(3) != 1) dout = dout.contiguous();
-  check_bhsd(dout, "dout");
-  check_bhsd(q, "q");
-  lse = check_bwd_args(q, k, v, lse);
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
-  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
-  auto dq_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  // dkv writes one fp32 partial slab per q-head of each GQA group (full
-  // grid occupancy at high TP); sum + cast here
-  int group = HQ / HKV;
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto dk_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  auto dv_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  launch_flash_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                   lse.data_ptr(), delta.data_ptr(), dq_mem.data_ptr(),
-                   dk_part.data_ptr(), dv_part.data_ptr(), B, HQ, HKV, SQ,
-                   SKV, D, causal, (float)scale, (int)window, qs, ks, vs, ds,
-                   cur_stream());
-  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
-  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
-  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
-          dv_mem.permute({1, 2, 0, 3})};
-}
-
 static void check_kv_range(const torch::Tensor& t, const torch::Tensor& q,
                            const char* name) {
   TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name,
@@ -447,45 +413,6 @@ std::vector<torch::Tensor> flash_attn_fwd_range(
                          vs, kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
                          cur_stream());
   return {o_mem.permute({1, 2, 0, 3}), lse};
-}
-
-std::vector<torch::Tensor> flash_attn_bwd_range(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
-    torch::Tensor o, torch::Tensor lse, torch::Tensor kv_lo,
-    torch::Tensor kv_hi, bool causal, double scale, long window) {
-  if (dout.stride(3) != 1) dout = dout.contiguous();
-  check_bhsd(dout, "dout");
-  check_bhsd(q, "q");
-  lse = check_bwd_args(q, k, v, lse);
-  check_kv_range(kv_lo, q, "kv_lo");
-  check_kv_range(kv_hi, q, "kv_hi");
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
-  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
-  // every q-block / key-block stores its whole slab (zeros where the range
-  // leaves it no work), so torch::empty is safe here too
-  auto dq_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  int group = HQ / HKV;
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto dk_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  auto dv_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  launch_flash_bwd_range(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                         v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                         dq_mem.data_ptr(), dk_part.data_ptr(),
-                         dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
-                         (float)scale, (int)window, qs, ks, vs, ds,
-                         kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
-                         cur_stream());
-  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
-  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
-  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
-          dv_mem.permute({1, 2, 0, 3})};
 }
 
 static void check_seg_bound(const torch::Tensor& t, const torch::Tensor& q,
@@ -531,42 +458,106 @@ std::vector<torch::Tensor> flash_attn_fwd_seg(
   return {o_mem.permute({1, 2, 0, 3}), lse};
 }
 
-std::vector<torch::Tensor> flash_attn_bwd_seg(
-    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
-    torch::Tensor o, torch::Tensor lse, torch::Tensor q_start,
-    torch::Tensor k_end, double scale, long window) {
+// Shared body of the six backward bindings. mode 0: dense, 1: per-row key
+// range (a = kv_lo, b = kv_hi, int32 [B]), 2: packed sequences (a = q_start,
+// b = k_end, int32 [B, S]; causal, S_q == S_kv). pipe selects the dK/dV
+// kernel: true = the pipelined kernel (flash_attn_bwd_dkv_pipe.hip, the
+// default), false = the single-buffered kernel it replaced (the *_sbuf
+// bindings, kept for A/B; bit-identical). dQ, delta and every check are
+// shared.
+static std::vector<torch::Tensor> flash_bwd_common(
+    int mode, bool pipe, torch::Tensor dout, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, torch::Tensor o, torch::Tensor lse, const torch::Tensor* a,
+    const torch::Tensor* b, bool causal, double scale, long window) {
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
   lse = check_bwd_args(q, k, v, lse);
-  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
+  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
       D = (int)q.size(3);
-  int HKV = (int)k.size(1);
-  TORCH_CHECK(k.size(2) == S, "segmented attention needs S_q == S_kv");
-  check_seg_bound(q_start, q, "q_start");
-  check_seg_bound(k_end, q, "k_end");
-  auto delta = attn_delta(dout, o);  // [B, HQ, S] f32, fused
-  // every q-block / key-block stores its whole slab, so torch::empty is safe
-  auto dq_mem = torch::empty({S, B, HQ, D}, q.options());
+  int HKV = (int)k.size(1), SKV = (int)k.size(2);
+  if (mode == 1) {
+    check_kv_range(*a, q, "kv_lo");
+    check_kv_range(*b, q, "kv_hi");
+  }
+  if (mode == 2) {
+    TORCH_CHECK(SKV == SQ, "segmented attention needs S_q == S_kv");
+    check_seg_bound(*a, q, "q_start");
+    check_seg_bound(*b, q, "k_end");
+  } else {
+    TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
+  }
+  // the pipelined kernel addresses a 64-row tile with 32-bit byte offsets
+  TORCH_CHECK(!pipe || (q.stride(2) >= 0 && q.stride(2) < (1L << 24) &&
+                        dout.stride(2) >= 0 && dout.stride(2) < (1L << 24)),
+              "q / dout sequence stride must be below 2^24 elements");
+  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
+  // every q-block / key-block stores its whole slab (zeros where a range or
+  // a segment leaves it no work), so torch::empty is safe
+  auto dq_mem = torch::empty({SQ, B, HQ, D}, q.options());
+  // dkv writes one fp32 partial slab per q-head of each GQA group (full
+  // grid occupancy at high TP); sum + cast here
   int group = HQ / HKV;
   auto f32 = q.options().dtype(torch::kFloat32);
-  auto dk_part = torch::empty({group, S, B, HKV, D}, f32);
-  auto dv_part = torch::empty({group, S, B, HKV, D}, f32);
+  auto dk_part = torch::empty({group, SKV, B, HKV, D}, f32);
+  auto dv_part = torch::empty({group, SKV, B, HKV, D}, f32);
   long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
   long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
   long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
   long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  launch_flash_bwd_seg(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                       v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                       dq_mem.data_ptr(), dk_part.data_ptr(),
-                       dv_part.data_ptr(), B, HQ, HKV, S, D, (float)scale,
-                       (int)window, qs, ks, vs, ds, q_start.data_ptr<int>(),
-                       k_end.data_ptr<int>(), cur_stream());
+  if (mode == 0)
+    launch_flash_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                     v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                     dq_mem.data_ptr(), dk_part.data_ptr(),
+                     dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
+                     (float)scale, (int)window, qs, ks, vs, ds, pipe,
+                     cur_stream());
+  else if (mode == 1)
+    launch_flash_bwd_range(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                           v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                           dq_mem.data_ptr(), dk_part.data_ptr(),
+                           dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
+                           (float)scale, (int)window, qs, ks, vs, ds,
+                           a->data_ptr<int>(), b->data_ptr<int>(), pipe,
+                           cur_stream());
+  else
+    launch_flash_bwd_seg(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
+                         v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
+                         dq_mem.data_ptr(), dk_part.data_ptr(),
+                         dv_part.data_ptr(), B, HQ, HKV, SQ, D, (float)scale,
+                         (int)window, qs, ks, vs, ds, a->data_ptr<int>(),
+                         b->data_ptr<int>(), pipe, cur_stream());
   auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
   auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
   return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
           dv_mem.permute({1, 2, 0, 3})};
 }
+
+#define BWD_BINDINGS(SUFFIX, PIPE)                                            \
+  std::vector<torch::Tensor> flash_attn_bwd##SUFFIX(                          \
+      torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
+      torch::Tensor o, torch::Tensor lse, bool causal, double scale,          \
+      long window) {                                                          \
+    return flash_bwd_common(0, PIPE, dout, q, k, v, o, lse, nullptr, nullptr, \
+                            causal, scale, window);                           \
+  }                                                                           \
+  std::vector<torch::Tensor> flash_attn_bwd_range##SUFFIX(                    \
+      torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
+      torch::Tensor o, torch::Tensor lse, torch::Tensor kv_lo,                \
+      torch::Tensor kv_hi, bool causal, double scale, long window) {          \
+    return flash_bwd_common(1, PIPE, dout, q, k, v, o, lse, &kv_lo, &kv_hi,   \
+                            causal, scale, window);                           \
+  }                                                                           \
+  std::vector<torch::Tensor> flash_attn_bwd_seg##SUFFIX(                      \
+      torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
+      torch::Tensor o, torch::Tensor lse, torch::Tensor q_start,              \
+      torch::Tensor k_end, double scale, long window) {                       \
+    return flash_bwd_common(2, PIPE, dout, q, k, v, o, lse, &q_start, &k_end, \
+                            true, scale, window);                             \
+  }
+BWD_BINDINGS(, true)        // pipelined dK/dV (default)
+BWD_BINDINGS(_sbuf, false)  // the kernel it replaced, for A/B
+#undef BWD_BINDINGS
 
 torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
                        torch::Tensor tile_expert, torch::Tensor total_rows,
@@ -725,6 +716,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("q_start"),
         pybind11::arg("k_end"), pybind11::arg("scale"),
         pybind11::arg("window") = 0);
+  m.def("flash_attn_bwd_sbuf", &flash_attn_bwd_sbuf, pybind11::arg("dout"),
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
+  m.def("flash_attn_bwd_range_sbuf", &flash_attn_bwd_range_sbuf,
+        pybind11::arg("dout"), pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
+        pybind11::arg("kv_lo"), pybind11::arg("kv_hi"),
+        pybind11::arg("causal"), pybind11::arg("scale"),
+        pybind11::arg("window") = 0);
+  m.def("flash_attn_bwd_seg_sbuf", &flash_attn_bwd_seg_sbuf,
+        pybind11::arg("dout"), pybind11::arg("q"), pybind11::arg("k"),
+        pybind11::arg("v"), pybind11::arg("o"), pybind11::arg("lse"),
+        pybind11::arg("q_start"), pybind11::arg("k_end"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.def("flash_attn_fwd_v3", &flash_attn_fwd_v3, pybind11::arg("q"),

@@ -44,9 +44,15 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
   static_assert(!SEGMENTED || CAUSAL, "segments are causal");
   constexpr int BN = 256;  // keys per block
   // q tile 64 at 145 KB LDS = 1 block/CU. A BM=32 variant (79 KB, 2
-  // blocks/CU) measured SLOWER (14.7 vs 12.0 ms) — the kernel is
-  // MFMA-pipe-bound at 2 waves/SIMD already, and halving the tile
-  // doubles per-tile staging/barrier overhead.
+  // blocks/CU) measured SLOWER (14.7 vs 12.0 ms): halving the tile
+  // doubles per-tile staging/barrier overhead. This kernel is NOT
+  // MFMA-bound: about a fifth of a tile's cycles are MFMA issue; it reads
+  // Q/dO twice per tile with both fetches exposed after the closing
+  // barrier, and D = 128 spills (27 VGPRs, 112 B/lane scratch). It is kept
+  // verbatim as the A/B arm (*_sbuf bindings) of the pipelined kernel in
+  // flash_attn_bwd_dkv_pipe.hip, which does the same arithmetic and takes
+  // the whole backward call at the bench shape from 7.21 to 5.27 ms
+  // (profiles/README_dkv_pipeline.md).
   constexpr int BM = 64;
   // bottom-right causal alignment for S_q != S_kv (see flash_attn_fwd.hip)
   const int coff = SKV - SQ;
@@ -630,13 +636,30 @@ void launch_attn_delta(const void* dout, const void* o, void* delta, int SQ,
         dstr[1], dstr[2], ostr[0], ostr[1], ostr[2]);
 }
 
+// pipelined dK/dV kernel (flash_attn_bwd_dkv_pipe.hip), bit-equal to
+// flash_bwd_dkv_kernel above. mode 0: dense, 1: RANGED, 2: SEGMENTED.
+void launch_flash_dkv_pipe(const void* dout, const void* q, const void* k,
+                           const void* v, const void* lse, const void* delta,
+                           void* dk, void* dv, int B, int HQ, int HKV, int SQ,
+                           int SKV, int D, bool causal, float scale,
+                           int window, const long* qstr, const long* kstr,
+                           const long* vstr, const long* dostr, int mode,
+                           const int* bound_a, const int* bound_b,
+                           hipStream_t stream);
+
+// pipe = true: dK/dV by the pipelined kernel (the default); false: by
+// flash_bwd_dkv_kernel above (the A/B arm). dQ is the same kernel in both.
 void launch_flash_bwd(const void* dout, const void* q, const void* k,
                       const void* v, const void* lse, const void* delta,
                       void* dq, void* dk, void* dv, int B, int HQ, int HKV,
                       int SQ, int SKV, int D, bool causal, float scale,
                       int window, const long* qstr, const long* kstr,
-                      const long* vstr, const long* dostr,
+                      const long* vstr, const long* dostr, bool pipe,
                       hipStream_t stream) {
+  if (pipe)
+    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, SQ,
+                          SKV, D, causal, scale, window, qstr, kstr, vstr,
+                          dostr, 0, nullptr, nullptr, stream);
   dim3 blk(512);
   dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
   const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
@@ -644,6 +667,7 @@ void launch_flash_bwd(const void* dout, const void* q, const void* k,
   dim3 gq((SQ + bm - 1) / bm, B * HQ);
 #define CASE(DD, CC)                                                          \
   do {                                                                        \
+    if (!pipe)                                                                \
     flash_bwd_dkv_kernel<DD, CC><<<gkv, blk, 0, stream>>>(                    \
         (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
         (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,  \
@@ -679,8 +703,12 @@ void launch_flash_bwd_range(const void* dout, const void* q, const void* k,
                       int SQ, int SKV, int D, bool causal, float scale,
                       int window, const long* qstr, const long* kstr,
                       const long* vstr, const long* dostr,
-                      const int* kv_lo, const int* kv_hi,
+                      const int* kv_lo, const int* kv_hi, bool pipe,
                       hipStream_t stream) {
+  if (pipe)
+    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, SQ,
+                          SKV, D, causal, scale, window, qstr, kstr, vstr,
+                          dostr, 1, kv_lo, kv_hi, stream);
   dim3 blk(512);
   dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
   const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
@@ -688,6 +716,7 @@ void launch_flash_bwd_range(const void* dout, const void* q, const void* k,
   dim3 gq((SQ + bm - 1) / bm, B * HQ);
 #define CASE(DD, CC)                                                          \
   do {                                                                        \
+    if (!pipe)                                                                \
     flash_bwd_dkv_kernel<DD, CC, true><<<gkv, blk, 0, stream>>>(                    \
         (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
         (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,  \
@@ -727,7 +756,11 @@ void launch_flash_bwd_seg(const void* dout, const void* q, const void* k,
                       int S, int D, float scale, int window,
                       const long* qstr, const long* kstr, const long* vstr,
                       const long* dostr, const int* q_start, const int* k_end,
-                      hipStream_t stream) {
+                      bool pipe, hipStream_t stream) {
+  if (pipe)
+    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, S, S,
+                          D, true, scale, window, qstr, kstr, vstr, dostr, 2,
+                          q_start, k_end, stream);
   dim3 blk(512);
   dim3 gkv((S + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
   const bool small = ((long)((S + 255) / 256) * B * HQ) < 512;
@@ -735,6 +768,7 @@ void launch_flash_bwd_seg(const void* dout, const void* q, const void* k,
   dim3 gq((S + bm - 1) / bm, B * HQ);
 #define CASE(DD)                                                              \
   do {                                                                        \
+    if (!pipe)                                                                \
     flash_bwd_dkv_kernel<DD, true, false, true><<<gkv, blk, 0, stream>>>(     \
         (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
         (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, S,   \

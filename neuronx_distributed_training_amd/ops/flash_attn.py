@@ -58,10 +58,27 @@ def _fwd_fn(kern, sq=None, skv=None):
     return kern.flash_attn_fwd
 
 
+def _dkv_arm() -> str:
+    """dK/dV kernel of the v2 backward: 'pipe' = pipelined tile loop
+    (default), 'sbuf' = the single-buffered kernel it replaced, kept for
+    A/B; the two are bit-identical. NXDT_ATTN_DKV=pipe/sbuf overrides."""
+    env = os.environ.get("NXDT_ATTN_DKV", "") or "pipe"
+    if env not in ("pipe", "sbuf"):
+        raise ValueError(f"NXDT_ATTN_DKV must be 'pipe' or 'sbuf', got {env!r}")
+    return env
+
+
+def v2_bwd_fn(kern, kind=""):
+    """The v2 backward binding of `kind` ('' dense, '_range', '_seg') for
+    the dK/dV arm NXDT_ATTN_DKV selects."""
+    suffix = "_sbuf" if _dkv_arm() == "sbuf" else ""
+    return getattr(kern, f"flash_attn_bwd{kind}{suffix}")
+
+
 def _bwd_fn(kern, sq=None, skv=None):
     if _attn_version() == "3" and (sq is None or sq == skv):
         return kern.flash_attn_bwd_v3
-    return kern.flash_attn_bwd
+    return v2_bwd_fn(kern)
 
 
 def mask_to_kv_range_tensors(attention_mask):
@@ -247,12 +264,12 @@ class _FlashAttnFn(torch.autograd.Function):
             q, k, v, o, lse = ctx.saved_tensors
         kern = kernels_for(q)
         if kern is not None and ctx.segmented:
-            dq, dk, dv = kern.flash_attn_bwd_seg(
+            dq, dk, dv = v2_bwd_fn(kern, "_seg")(
                 do, q, k, v, o, lse, q_start, k_end, ctx.scale, ctx.window
             )
             return (dq, dk, dv) + none7
         if kern is not None and ctx.ranged:
-            dq, dk, dv = kern.flash_attn_bwd_range(
+            dq, dk, dv = v2_bwd_fn(kern, "_range")(
                 do, q, k, v, o, lse, kv_lo, kv_hi, ctx.causal, ctx.scale,
                 ctx.window,
             )

@@ -38,7 +38,7 @@ import torch
 import torch.distributed as dist
 
 from ..parallel import state as ps
-from .flash_attn import _FlashAttnFn, _cpu_ref_fwd, _make_mask
+from .flash_attn import _FlashAttnFn, _cpu_ref_fwd, _make_mask, v2_bwd_fn
 from . import kernels_for
 
 
@@ -103,7 +103,7 @@ def _cpu_block_bwd(do, q, k, v, out, lse, causal, scale):
 
 def _bwd_block(kern, do, q, k, v, out, lse, causal, scale):
     if kern is not None:
-        return kern.flash_attn_bwd(
+        return v2_bwd_fn(kern)(
             do.contiguous(), q, k, v, out, lse, causal, scale
         )
     return _cpu_block_bwd(do, q, k, v, out, lse, causal, scale)
