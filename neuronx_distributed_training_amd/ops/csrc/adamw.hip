@@ -11,6 +11,7 @@
 //     shard) written alongside the fp32 master — removes the separate
 //     master->bf16 cast pass AND the bf16 param copy pass.
 #include "common.h"
+#include "launch.h"
 
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                              float* __restrict__ m, float* __restrict__ v,

@@ -5,70 +5,7 @@
 
 #include <c10/hip/HIPStream.h>
 
-extern "C" {
-void launch_rmsnorm_fwd(const void*, const void*, void*, void*, long, int,
-                        float, hipStream_t);
-void launch_rmsnorm_bwd(const void*, const void*, const void*, const void*,
-                        void*, void*, long, int, hipStream_t);
-void launch_swiglu_fwd(const void*, void*, long, int, hipStream_t);
-void launch_swiglu_bwd(const void*, const void*, void*, long, int,
-                       hipStream_t);
-void launch_rope_fwd(const void*, const void*, const void*, void*, int, int,
-                     int, int, const long*, int, int, float, hipStream_t);
-void launch_adamw(void*, const void*, void*, void*, const void*, const void*,
-                  void*, long, float, float, float, float, float, int,
-                  hipStream_t);
-void launch_flash_fwd(const void*, const void*, const void*, void*, void*,
-                      int, int, int, int, int, int, bool, float, int,
-                      const long*, const long*, const long*, hipStream_t);
-void launch_flash_fwd_dbuf(const void*, const void*, const void*, void*,
-                           void*, int, int, int, int, int, int, bool, float,
-                           int, const long*, const long*, const long*,
-                           hipStream_t);
-void launch_flash_bwd(const void*, const void*, const void*, const void*,
-                      const void*, const void*, void*, void*, void*, int, int,
-                      int, int, int, int, bool, float, int, const long*,
-                      const long*, const long*, const long*, bool,
-                      hipStream_t);
-void launch_attn_delta(const void*, const void*, void*, int, int, int, int,
-                       const long*, const long*, hipStream_t);
-void launch_flash_fwd_range(const void*, const void*, const void*, void*,
-                            void*, int, int, int, int, int, int, bool, float,
-                            int, const long*, const long*, const long*,
-                            const int*, const int*, hipStream_t);
-void launch_flash_bwd_range(const void*, const void*, const void*,
-                            const void*, const void*, const void*, void*,
-                            void*, void*, int, int, int, int, int, int, bool,
-                            float, int, const long*, const long*, const long*,
-                            const long*, const int*, const int*, bool,
-                            hipStream_t);
-void launch_flash_fwd_seg(const void*, const void*, const void*, void*, void*,
-                          int, int, int, int, int, float, int, const long*,
-                          const long*, const long*, const int*, const int*,
-                          hipStream_t);
-void launch_flash_bwd_seg(const void*, const void*, const void*, const void*,
-                          const void*, const void*, void*, void*, void*, int,
-                          int, int, int, int, float, int, const long*,
-                          const long*, const long*, const long*, const int*,
-                          const int*, bool, hipStream_t);
-void launch_mfma_probe(const void*, const void*, void*, hipStream_t);
-void launch_mfma_probe32(const void*, const void*, void*, hipStream_t);
-void launch_flash_fwd_v3(const void*, const void*, const void*, void*, void*,
-                         int, int, int, int, int, bool, float, int,
-                         const long*, const long*, const long*, hipStream_t);
-void launch_flash_bwd_v3(const void*, const void*, const void*, const void*,
-                         const void*, const void*, void*, void*, void*, int,
-                         int, int, int, int, bool, float, int, const long*,
-                         const long*, const long*, const long*, hipStream_t);
-void launch_moe_gemm(const void*, const void*, void*, const int*, const int*,
-                     int, int, int, long, bool, hipStream_t);
-void launch_moe_wgrad(const void*, const void*, void*, const int*, int, int,
-                      int, hipStream_t);
-void launch_ce_fwd(const void*, const void*, void*, void*, void*, long, int,
-                   long, hipStream_t);
-void launch_ce_bwd(const void*, const void*, const void*, const void*,
-                   const void*, void*, long, int, long, hipStream_t);
-}
+#include "launch.h"
 
 namespace {
 
@@ -244,137 +181,6 @@ static torch::Tensor check_bwd_args(const torch::Tensor& q,
   return lse.contiguous();
 }
 
-static torch::Tensor attn_delta(torch::Tensor dout, torch::Tensor o) {
-  // fused rowsum(dO . O) -> [B, HQ, SQ] fp32 (no fp32 materialization)
-  auto oc = o.stride(3) == 1 ? o : o.contiguous();
-  int B = (int)dout.size(0), HQ = (int)dout.size(1), SQ = (int)dout.size(2),
-      D = (int)dout.size(3);
-  auto delta = torch::empty(
-      {B, HQ, SQ}, dout.options().dtype(torch::kFloat32));
-  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  long os_[3] = {oc.stride(2), oc.stride(0), oc.stride(1)};
-  launch_attn_delta(dout.data_ptr(), oc.data_ptr(), delta.data_ptr(), SQ, B,
-                    HQ, D, ds, os_, cur_stream());
-  return delta;
-}
-
-std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q, torch::Tensor k,
-                                             torch::Tensor v, bool causal,
-                                             double scale, long window) {
-  // T12 swapped-operand forward (ROADMAP §1); dark until HW-validated
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
-  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1);
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(k.size(2) == S, "v3 kernel requires S_q == S_kv (use v2)");
-  auto o_mem = torch::empty({S, B, HQ, D}, q.options());
-  auto lse = torch::empty({B, HQ, S}, q.options().dtype(torch::kFloat32));
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  launch_flash_fwd_v3(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                      o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, S, D,
-                      causal, (float)scale, (int)window, qs, ks, vs,
-                      cur_stream());
-  return {o_mem.permute({1, 2, 0, 3}), lse};
-}
-
-std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
-                                             torch::Tensor q, torch::Tensor k,
-                                             torch::Tensor v, torch::Tensor o,
-                                             torch::Tensor lse, bool causal,
-                                             double scale, long window) {
-  if (dout.stride(3) != 1) dout = dout.contiguous();
-  check_bhsd(dout, "dout");
-  check_bhsd(q, "q");
-  lse = check_bwd_args(q, k, v, lse);
-  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1);
-  TORCH_CHECK(k.size(2) == S, "v3 kernel requires S_q == S_kv (use v2)");
-  auto delta = attn_delta(dout, o);
-  auto dq_mem = torch::empty({S, B, HQ, D}, q.options());
-  int group = HQ / HKV;
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto dk_part = torch::empty({group, S, B, HKV, D}, f32);
-  auto dv_part = torch::empty({group, S, B, HKV, D}, f32);
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  long dstr[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  launch_flash_bwd_v3(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                      v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                      dq_mem.data_ptr(), dk_part.data_ptr(),
-                      dv_part.data_ptr(), B, HQ, HKV, S, D, causal,
-                      (float)scale, (int)window, qs, ks, vs, dstr,
-                      cur_stream());
-  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
-  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
-  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
-          dv_mem.permute({1, 2, 0, 3})};
-}
-
-std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
-                                          torch::Tensor v, bool causal,
-                                          double scale, long window) {
-  // q/k/v: logical [b, h, s, d], arbitrary strides (views of the QKV GEMM
-  // output). Returns O as a [b, h, s, d] view of [s, b, h, d] storage.
-  // S_q != S_kv supported; causal is then bottom-right aligned (decode /
-  // ring-attention half-block convention, requires S_kv >= S_q).
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
-  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
-  auto o_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  auto lse = torch::empty({B, HQ, SQ}, q.options().dtype(torch::kFloat32));
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  // double-buffered staging variant: bit-identical output, measured
-  // +3.0% (bench shape) / +1.8% (TP=8 shape) over the single-buffer
-  // kernel -> default (the single-buffer launcher remains for A/B)
-  launch_flash_fwd_dbuf(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                        o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, SQ,
-                        SKV, D, causal, (float)scale, (int)window, qs, ks,
-                        vs, cur_stream());
-  return {o_mem.permute({1, 2, 0, 3}), lse};
-}
-
-std::vector<torch::Tensor> flash_attn_fwd_sbuf(torch::Tensor q,
-                                               torch::Tensor k,
-                                               torch::Tensor v, bool causal,
-                                               double scale, long window) {
-  // A/B reference: the SINGLE-buffered staging kernel (two barriers per
-  // tile) that the double-buffered default replaced — bit-identical
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
-  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
-  auto o_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  auto lse = torch::empty({B, HQ, SQ}, q.options().dtype(torch::kFloat32));
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  launch_flash_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                        o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, SQ,
-                        SKV, D, causal, (float)scale, (int)window, qs, ks,
-                        vs, cur_stream());
-  return {o_mem.permute({1, 2, 0, 3}), lse};
-}
-
 static void check_kv_range(const torch::Tensor& t, const torch::Tensor& q,
                            const char* name) {
   TORCH_CHECK(t.is_cuda() && t.device() == q.device(), name,
@@ -383,36 +189,6 @@ static void check_kv_range(const torch::Tensor& t, const torch::Tensor& q,
   TORCH_CHECK(t.dim() == 1 && t.size(0) == q.size(0), name,
               " must have shape [B]");
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-}
-
-std::vector<torch::Tensor> flash_attn_fwd_range(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo,
-    torch::Tensor kv_hi, bool causal, double scale, long window) {
-  // flash_attn_fwd with a per-batch-row visible key range
-  // [kv_lo[b], kv_hi[b]) (padded batches). Values are trusted to satisfy
-  // 0 <= lo <= hi <= S_kv; the Python op clamps them.
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
-  check_kv_range(kv_lo, q, "kv_lo");
-  check_kv_range(kv_hi, q, "kv_hi");
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
-  TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
-  auto o_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  auto lse = torch::empty({B, HQ, SQ}, q.options().dtype(torch::kFloat32));
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  launch_flash_fwd_range(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                         o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, SQ,
-                         SKV, D, causal, (float)scale, (int)window, qs, ks,
-                         vs, kv_lo.data_ptr<int>(), kv_hi.data_ptr<int>(),
-                         cur_stream());
-  return {o_mem.permute({1, 2, 0, 3}), lse};
 }
 
 static void check_seg_bound(const torch::Tensor& t, const torch::Tensor& q,
@@ -426,111 +202,244 @@ static void check_seg_bound(const torch::Tensor& t, const torch::Tensor& q,
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
 
-std::vector<torch::Tensor> flash_attn_fwd_seg(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor q_start,
-    torch::Tensor k_end, double scale, long window) {
-  // causal flash_attn_fwd over packed sequences: query i of row b sees keys
-  // q_start[b,i] <= j <= i (block-diagonal mask). k_end[b,j] is one past
-  // the last query that sees key j. Values are trusted to be non-decreasing
-  // along each row with 0 <= q_start[b,i] <= i < k_end[b,i] <= S; the
-  // Python op derives them from segment ids.
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
-  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1);
-  TORCH_CHECK(k.size(2) == S, "segmented attention needs S_q == S_kv");
-  check_seg_bound(q_start, q, "q_start");
-  check_seg_bound(k_end, q, "k_end");
-  TORCH_CHECK(D == 128 || D == 64, "head_dim must be 64 or 128");
-  TORCH_CHECK(HQ % HKV == 0, "GQA head mismatch");
-  auto o_mem = torch::empty({S, B, HQ, D}, q.options());
-  auto lse = torch::empty({B, HQ, S}, q.options().dtype(torch::kFloat32));
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  launch_flash_fwd_seg(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                       o_mem.data_ptr(), lse.data_ptr(), B, HQ, HKV, S, D,
-                       (float)scale, (int)window, qs, ks, vs,
-                       q_start.data_ptr<int>(), k_end.data_ptr<int>(),
-                       cur_stream());
+// (seq, batch, head) element strides of a logical [b, h, s, d] tensor
+static void sbh_strides(const torch::Tensor& t, long (&s)[3]) {
+  s[0] = t.stride(2);
+  s[1] = t.stride(0);
+  s[2] = t.stride(1);
+}
+
+// The launch arguments that q / k / v and the scalars decide; q, k and v have
+// passed check_bhsd. Outputs, the backward tensors and the mask bounds are
+// null / DENSE until the caller sets them.
+static FlashArgs flash_args(const torch::Tensor& q, const torch::Tensor& k,
+                            const torch::Tensor& v, bool causal, double scale,
+                            long window) {
+  FlashArgs a{};
+  a.q = q.data_ptr();
+  a.k = k.data_ptr();
+  a.v = v.data_ptr();
+  a.B = (int)q.size(0);
+  a.HQ = (int)q.size(1);
+  a.SQ = (int)q.size(2);
+  a.D = (int)q.size(3);
+  a.HKV = (int)k.size(1);
+  a.SKV = (int)k.size(2);
+  a.causal = causal;
+  a.scale = (float)scale;
+  a.window = (int)window;
+  sbh_strides(q, a.qs);
+  sbh_strides(k, a.ks);
+  sbh_strides(v, a.vs);
+  return a;
+}
+
+static void set_mask(FlashArgs& a, FlashArgs::Mask mask,
+                     const torch::Tensor* lo, const torch::Tensor* hi) {
+  a.mask = mask;
+  if (mask != FlashArgs::DENSE) {
+    a.bound_a = lo->data_ptr<int>();
+    a.bound_b = hi->data_ptr<int>();
+  }
+}
+
+static torch::Tensor attn_delta(torch::Tensor dout, torch::Tensor o) {
+  // fused rowsum(dO . O) -> [B, HQ, SQ] fp32 (no fp32 materialization)
+  auto oc = o.stride(3) == 1 ? o : o.contiguous();
+  int B = (int)dout.size(0), HQ = (int)dout.size(1), SQ = (int)dout.size(2),
+      D = (int)dout.size(3);
+  auto delta = torch::empty(
+      {B, HQ, SQ}, dout.options().dtype(torch::kFloat32));
+  long ds[3], os_[3];
+  sbh_strides(dout, ds);
+  sbh_strides(oc, os_);
+  launch_attn_delta(dout.data_ptr(), oc.data_ptr(), delta.data_ptr(), SQ, B,
+                    HQ, D, ds, os_, cur_stream());
+  return delta;
+}
+
+// Allocates O and LSE, runs launch(a, stream) and returns O as a
+// [b, h, s, d] view of its [s, b, h, d] storage, and LSE [B, HQ, SQ] fp32.
+template <class Launch>
+static std::vector<torch::Tensor> flash_fwd_run(FlashArgs a,
+                                                const torch::Tensor& q,
+                                                Launch launch) {
+  auto o_mem = torch::empty({a.SQ, a.B, a.HQ, a.D}, q.options());
+  auto lse =
+      torch::empty({a.B, a.HQ, a.SQ}, q.options().dtype(torch::kFloat32));
+  a.o = o_mem.data_ptr();
+  a.lse = lse.data_ptr();
+  launch(a, cur_stream());
   return {o_mem.permute({1, 2, 0, 3}), lse};
 }
 
-// Shared body of the six backward bindings. mode 0: dense, 1: per-row key
-// range (a = kv_lo, b = kv_hi, int32 [B]), 2: packed sequences (a = q_start,
-// b = k_end, int32 [B, S]; causal, S_q == S_kv). pipe selects the dK/dV
-// kernel: true = the pipelined kernel (flash_attn_bwd_dkv_pipe.hip, the
-// default), false = the single-buffered kernel it replaced (the *_sbuf
-// bindings, kept for A/B; bit-identical). dQ, delta and every check are
-// shared.
-static std::vector<torch::Tensor> flash_bwd_common(
-    int mode, bool pipe, torch::Tensor dout, torch::Tensor q, torch::Tensor k,
-    torch::Tensor v, torch::Tensor o, torch::Tensor lse, const torch::Tensor* a,
-    const torch::Tensor* b, bool causal, double scale, long window) {
+// delta, the outputs, launch(a, stream), and the sum over the GQA partial
+// slabs; dout, q and lse are the tensors handed to the kernels.
+template <class Launch>
+static std::vector<torch::Tensor> flash_bwd_run(FlashArgs a,
+                                                const torch::Tensor& dout,
+                                                const torch::Tensor& q,
+                                                const torch::Tensor& o,
+                                                const torch::Tensor& lse,
+                                                Launch launch) {
+  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
+  // every q-block / key-block stores its whole slab (zeros where a range or
+  // a segment leaves it no work), so torch::empty is safe
+  auto dq_mem = torch::empty({a.SQ, a.B, a.HQ, a.D}, q.options());
+  // dkv writes one fp32 partial slab per q-head of each GQA group (full
+  // grid occupancy at high TP); sum + cast here
+  int group = a.HQ / a.HKV;
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto dk_part = torch::empty({group, a.SKV, a.B, a.HKV, a.D}, f32);
+  auto dv_part = torch::empty({group, a.SKV, a.B, a.HKV, a.D}, f32);
+  a.dout = dout.data_ptr();
+  sbh_strides(dout, a.ds);
+  a.lse = lse.data_ptr();
+  a.delta = delta.data_ptr();
+  a.dq = dq_mem.data_ptr();
+  a.dk = dk_part.data_ptr();
+  a.dv = dv_part.data_ptr();
+  launch(a, cur_stream());
+  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
+  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
+  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
+          dv_mem.permute({1, 2, 0, 3})};
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_v3(torch::Tensor q, torch::Tensor k,
+                                             torch::Tensor v, bool causal,
+                                             double scale, long window) {
+  // T12 swapped-operand forward (ROADMAP §1); dark until HW-validated
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  FlashArgs a = flash_args(q, k, v, causal, scale, window);
+  TORCH_CHECK(a.D == 128 || a.D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(a.SKV == a.SQ, "v3 kernel requires S_q == S_kv (use v2)");
+  return flash_fwd_run(a, q, launch_flash_fwd_v3);
+}
+
+std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
+                                             torch::Tensor q, torch::Tensor k,
+                                             torch::Tensor v, torch::Tensor o,
+                                             torch::Tensor lse, bool causal,
+                                             double scale, long window) {
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
   lse = check_bwd_args(q, k, v, lse);
-  int B = (int)q.size(0), HQ = (int)q.size(1), SQ = (int)q.size(2),
-      D = (int)q.size(3);
-  int HKV = (int)k.size(1), SKV = (int)k.size(2);
-  if (mode == 1) {
-    check_kv_range(*a, q, "kv_lo");
-    check_kv_range(*b, q, "kv_hi");
+  FlashArgs a = flash_args(q, k, v, causal, scale, window);
+  TORCH_CHECK(a.SKV == a.SQ, "v3 kernel requires S_q == S_kv (use v2)");
+  return flash_bwd_run(a, dout, q, o, lse, launch_flash_bwd_v3);
+}
+
+// Shared body of the four forward bindings. q/k/v: logical [b, h, s, d],
+// arbitrary strides (views of the QKV GEMM output). S_q != S_kv supported;
+// causal is then bottom-right aligned (decode / ring-attention half-block
+// convention, requires S_kv >= S_q). dbuf selects the kernel: true = the
+// double-buffered staging kernel (the default: bit-identical output,
+// measured +3.0% (bench shape) / +1.8% (TP=8 shape)), false = the
+// single-buffered kernel it replaced (flash_attn_fwd_sbuf, kept for A/B;
+// DENSE only).
+// RANGED: per-batch-row visible key range [kv_lo[b], kv_hi[b]) (padded
+// batches), lo = kv_lo, hi = kv_hi, int32 [B]. Values are trusted to satisfy
+// 0 <= lo <= hi <= S_kv; the Python op clamps them.
+// SEGMENTED: causal attention over packed sequences: query i of row b sees
+// keys q_start[b,i] <= j <= i (block-diagonal mask); k_end[b,j] is one past
+// the last query that sees key j. lo = q_start, hi = k_end, int32 [B, S].
+// Values are trusted to be non-decreasing along each row with
+// 0 <= q_start[b,i] <= i < k_end[b,i] <= S; the Python op derives them from
+// segment ids.
+static std::vector<torch::Tensor> flash_fwd_common(
+    bool dbuf, FlashArgs::Mask mask, torch::Tensor q, torch::Tensor k,
+    torch::Tensor v, const torch::Tensor* lo, const torch::Tensor* hi,
+    bool causal, double scale, long window) {
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  FlashArgs a = flash_args(q, k, v, causal, scale, window);
+  if (mask == FlashArgs::RANGED) {
+    check_kv_range(*lo, q, "kv_lo");
+    check_kv_range(*hi, q, "kv_hi");
   }
-  if (mode == 2) {
-    TORCH_CHECK(SKV == SQ, "segmented attention needs S_q == S_kv");
-    check_seg_bound(*a, q, "q_start");
-    check_seg_bound(*b, q, "k_end");
+  if (mask == FlashArgs::SEGMENTED) {
+    TORCH_CHECK(a.SKV == a.SQ, "segmented attention needs S_q == S_kv");
+    check_seg_bound(*lo, q, "q_start");
+    check_seg_bound(*hi, q, "k_end");
+  }
+  TORCH_CHECK(a.D == 128 || a.D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(a.HQ % a.HKV == 0, "GQA head mismatch");
+  if (mask != FlashArgs::SEGMENTED)
+    TORCH_CHECK(!causal || a.SKV >= a.SQ, "causal needs S_kv >= S_q");
+  set_mask(a, mask, lo, hi);
+  return flash_fwd_run(a, q,
+                       dbuf ? launch_flash_fwd_dbuf : launch_flash_fwd);
+}
+
+std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
+                                          torch::Tensor v, bool causal,
+                                          double scale, long window) {
+  return flash_fwd_common(true, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
+                          causal, scale, window);
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_sbuf(torch::Tensor q,
+                                               torch::Tensor k,
+                                               torch::Tensor v, bool causal,
+                                               double scale, long window) {
+  return flash_fwd_common(false, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
+                          causal, scale, window);
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_range(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo,
+    torch::Tensor kv_hi, bool causal, double scale, long window) {
+  return flash_fwd_common(true, FlashArgs::RANGED, q, k, v, &kv_lo, &kv_hi,
+                          causal, scale, window);
+}
+
+std::vector<torch::Tensor> flash_attn_fwd_seg(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor q_start,
+    torch::Tensor k_end, double scale, long window) {
+  return flash_fwd_common(true, FlashArgs::SEGMENTED, q, k, v, &q_start,
+                          &k_end, true, scale, window);
+}
+
+// Shared body of the six backward bindings; mask, lo and hi as in
+// flash_fwd_common. pipe selects the dK/dV kernel: true = the pipelined
+// kernel (flash_attn_bwd_dkv_pipe.hip, the default), false = the
+// single-buffered kernel it replaced (the *_sbuf bindings, kept for A/B;
+// bit-identical). dQ, delta and every check are shared.
+static std::vector<torch::Tensor> flash_bwd_common(
+    FlashArgs::Mask mask, bool pipe, torch::Tensor dout, torch::Tensor q,
+    torch::Tensor k, torch::Tensor v, torch::Tensor o, torch::Tensor lse,
+    const torch::Tensor* lo, const torch::Tensor* hi, bool causal,
+    double scale, long window) {
+  if (dout.stride(3) != 1) dout = dout.contiguous();
+  check_bhsd(dout, "dout");
+  check_bhsd(q, "q");
+  lse = check_bwd_args(q, k, v, lse);
+  FlashArgs a = flash_args(q, k, v, causal, scale, window);
+  if (mask == FlashArgs::RANGED) {
+    check_kv_range(*lo, q, "kv_lo");
+    check_kv_range(*hi, q, "kv_hi");
+  }
+  if (mask == FlashArgs::SEGMENTED) {
+    TORCH_CHECK(a.SKV == a.SQ, "segmented attention needs S_q == S_kv");
+    check_seg_bound(*lo, q, "q_start");
+    check_seg_bound(*hi, q, "k_end");
   } else {
-    TORCH_CHECK(!causal || SKV >= SQ, "causal needs S_kv >= S_q");
+    TORCH_CHECK(!causal || a.SKV >= a.SQ, "causal needs S_kv >= S_q");
   }
   // the pipelined kernel addresses a 64-row tile with 32-bit byte offsets
   TORCH_CHECK(!pipe || (q.stride(2) >= 0 && q.stride(2) < (1L << 24) &&
                         dout.stride(2) >= 0 && dout.stride(2) < (1L << 24)),
               "q / dout sequence stride must be below 2^24 elements");
-  auto delta = attn_delta(dout, o);  // [B, HQ, SQ] f32, fused
-  // every q-block / key-block stores its whole slab (zeros where a range or
-  // a segment leaves it no work), so torch::empty is safe
-  auto dq_mem = torch::empty({SQ, B, HQ, D}, q.options());
-  // dkv writes one fp32 partial slab per q-head of each GQA group (full
-  // grid occupancy at high TP); sum + cast here
-  int group = HQ / HKV;
-  auto f32 = q.options().dtype(torch::kFloat32);
-  auto dk_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  auto dv_part = torch::empty({group, SKV, B, HKV, D}, f32);
-  long qs[3] = {q.stride(2), q.stride(0), q.stride(1)};
-  long ks[3] = {k.stride(2), k.stride(0), k.stride(1)};
-  long vs[3] = {v.stride(2), v.stride(0), v.stride(1)};
-  long ds[3] = {dout.stride(2), dout.stride(0), dout.stride(1)};
-  if (mode == 0)
-    launch_flash_bwd(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                     v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                     dq_mem.data_ptr(), dk_part.data_ptr(),
-                     dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
-                     (float)scale, (int)window, qs, ks, vs, ds, pipe,
-                     cur_stream());
-  else if (mode == 1)
-    launch_flash_bwd_range(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                           v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                           dq_mem.data_ptr(), dk_part.data_ptr(),
-                           dv_part.data_ptr(), B, HQ, HKV, SQ, SKV, D, causal,
-                           (float)scale, (int)window, qs, ks, vs, ds,
-                           a->data_ptr<int>(), b->data_ptr<int>(), pipe,
-                           cur_stream());
-  else
-    launch_flash_bwd_seg(dout.data_ptr(), q.data_ptr(), k.data_ptr(),
-                         v.data_ptr(), lse.data_ptr(), delta.data_ptr(),
-                         dq_mem.data_ptr(), dk_part.data_ptr(),
-                         dv_part.data_ptr(), B, HQ, HKV, SQ, D, (float)scale,
-                         (int)window, qs, ks, vs, ds, a->data_ptr<int>(),
-                         b->data_ptr<int>(), pipe, cur_stream());
-  auto dk_mem = dk_part.sum(0).to(torch::kBFloat16);
-  auto dv_mem = dv_part.sum(0).to(torch::kBFloat16);
-  return {dq_mem.permute({1, 2, 0, 3}), dk_mem.permute({1, 2, 0, 3}),
-          dv_mem.permute({1, 2, 0, 3})};
+  set_mask(a, mask, lo, hi);
+  return flash_bwd_run(a, dout, q, o, lse,
+                       [pipe](const FlashArgs& f, hipStream_t stream) {
+                         launch_flash_bwd(f, pipe, stream);
+                       });
 }
 
 #define BWD_BINDINGS(SUFFIX, PIPE)                                            \
@@ -538,22 +447,22 @@ static std::vector<torch::Tensor> flash_bwd_common(
       torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
       torch::Tensor o, torch::Tensor lse, bool causal, double scale,          \
       long window) {                                                          \
-    return flash_bwd_common(0, PIPE, dout, q, k, v, o, lse, nullptr, nullptr, \
-                            causal, scale, window);                           \
+    return flash_bwd_common(FlashArgs::DENSE, PIPE, dout, q, k, v, o, lse,    \
+                            nullptr, nullptr, causal, scale, window);         \
   }                                                                           \
   std::vector<torch::Tensor> flash_attn_bwd_range##SUFFIX(                    \
       torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
       torch::Tensor o, torch::Tensor lse, torch::Tensor kv_lo,                \
       torch::Tensor kv_hi, bool causal, double scale, long window) {          \
-    return flash_bwd_common(1, PIPE, dout, q, k, v, o, lse, &kv_lo, &kv_hi,   \
-                            causal, scale, window);                           \
+    return flash_bwd_common(FlashArgs::RANGED, PIPE, dout, q, k, v, o, lse,   \
+                            &kv_lo, &kv_hi, causal, scale, window);           \
   }                                                                           \
   std::vector<torch::Tensor> flash_attn_bwd_seg##SUFFIX(                      \
       torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,  \
       torch::Tensor o, torch::Tensor lse, torch::Tensor q_start,              \
       torch::Tensor k_end, double scale, long window) {                       \
-    return flash_bwd_common(2, PIPE, dout, q, k, v, o, lse, &q_start, &k_end, \
-                            true, scale, window);                             \
+    return flash_bwd_common(FlashArgs::SEGMENTED, PIPE, dout, q, k, v, o,     \
+                            lse, &q_start, &k_end, true, scale, window);      \
   }
 BWD_BINDINGS(, true)        // pipelined dK/dV (default)
 BWD_BINDINGS(_sbuf, false)  // the kernel it replaced, for A/B

@@ -5,6 +5,7 @@
 // recompute pass backward. The TP all-reduces (max / sum-exp / target
 // logit) stay in the Python wrapper (parallel/loss.py).
 #include "common.h"
+#include "launch.h"
 
 // logits [N, V] bf16 → per-row local max (f32), sumexp@max (f32),
 // target logit (f32; 0 when this shard doesn't own the target).

@@ -10,6 +10,7 @@
 // writes. dkv: BN=256 keys (32/wave), q-tile 64. dq: BM=256 (32/wave),
 // key tile 64.
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 // RANGED (both kernels): per-batch-row visible key range
 // [kv_lo[b], kv_hi[b]) on top of the causal / window mask, matching
@@ -636,165 +637,42 @@ void launch_attn_delta(const void* dout, const void* o, void* delta, int SQ,
         dstr[1], dstr[2], ostr[0], ostr[1], ostr[2]);
 }
 
-// pipelined dK/dV kernel (flash_attn_bwd_dkv_pipe.hip), bit-equal to
-// flash_bwd_dkv_kernel above. mode 0: dense, 1: RANGED, 2: SEGMENTED.
-void launch_flash_dkv_pipe(const void* dout, const void* q, const void* k,
-                           const void* v, const void* lse, const void* delta,
-                           void* dk, void* dv, int B, int HQ, int HKV, int SQ,
-                           int SKV, int D, bool causal, float scale,
-                           int window, const long* qstr, const long* kstr,
-                           const long* vstr, const long* dostr, int mode,
-                           const int* bound_a, const int* bound_b,
-                           hipStream_t stream);
-
-// pipe = true: dK/dV by the pipelined kernel (the default); false: by
-// flash_bwd_dkv_kernel above (the A/B arm). dQ is the same kernel in both.
-void launch_flash_bwd(const void* dout, const void* q, const void* k,
-                      const void* v, const void* lse, const void* delta,
-                      void* dq, void* dk, void* dv, int B, int HQ, int HKV,
-                      int SQ, int SKV, int D, bool causal, float scale,
-                      int window, const long* qstr, const long* kstr,
-                      const long* vstr, const long* dostr, bool pipe,
-                      hipStream_t stream) {
-  if (pipe)
-    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, SQ,
-                          SKV, D, causal, scale, window, qstr, kstr, vstr,
-                          dostr, 0, nullptr, nullptr, stream);
-  dim3 blk(512);
-  dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
-  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 gq((SQ + bm - 1) / bm, B * HQ);
-#define CASE(DD, CC)                                                          \
-  do {                                                                        \
-    if (!pipe)                                                                \
-    flash_bwd_dkv_kernel<DD, CC><<<gkv, blk, 0, stream>>>(                    \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,  \
-        SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],   \
-        kstr[1],                                                              \
-        kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);    \
-    if (small)                                                                \
-      flash_bwd_dq_kernel<DD, CC, 1><<<gq, blk, 0, stream>>>(                 \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);  \
-    else                                                                      \
-      flash_bwd_dq_kernel<DD, CC, 2><<<gq, blk, 0, stream>>>(                 \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);  \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASE(128, true); else CASE(128, false);
-  } else if (D == 64) {
-    if (causal) CASE(64, true); else CASE(64, false);
+// dK/dV by one of the two kernels (pipe = true: the pipelined kernel of
+// flash_attn_bwd_dkv_pipe.hip, the default; false: flash_bwd_dkv_kernel
+// above, the A/B arm, bit-equal), then dQ, the same kernel in both.
+void launch_flash_bwd(const FlashArgs& a, bool pipe, hipStream_t stream) {
+  const dim3 blk(512);
+  if (pipe) {
+    launch_flash_dkv_pipe(a, stream);
+  } else {
+    // one block per (kblock, b, hkv, g)
+    const dim3 gkv((a.SKV + 255) / 256, a.B * a.HQ);
+    dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+      flash_bwd_dkv_kernel<decltype(d)::value, decltype(c)::value,
+                           decltype(r)::value, decltype(s)::value>
+          <<<gkv, blk, 0, stream>>>(
+              (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
+              (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta,
+              (float*)a.dk, (float*)a.dv, a.SQ, a.SKV, a.B, a.HQ, a.HKV,
+              a.scale, a.window, a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1],
+              a.ks[2], a.vs[0], a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2],
+              a.bound_a, a.bound_b);
+    });
   }
-#undef CASE
-}
-
-// same grids as launch_flash_bwd, RANGED instantiations: kv_lo / kv_hi are
-// device int32 [B] with 0 <= lo <= hi <= SKV
-void launch_flash_bwd_range(const void* dout, const void* q, const void* k,
-                      const void* v, const void* lse, const void* delta,
-                      void* dq, void* dk, void* dv, int B, int HQ, int HKV,
-                      int SQ, int SKV, int D, bool causal, float scale,
-                      int window, const long* qstr, const long* kstr,
-                      const long* vstr, const long* dostr,
-                      const int* kv_lo, const int* kv_hi, bool pipe,
-                      hipStream_t stream) {
-  if (pipe)
-    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, SQ,
-                          SKV, D, causal, scale, window, qstr, kstr, vstr,
-                          dostr, 1, kv_lo, kv_hi, stream);
-  dim3 blk(512);
-  dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
-  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 gq((SQ + bm - 1) / bm, B * HQ);
-#define CASE(DD, CC)                                                          \
-  do {                                                                        \
-    if (!pipe)                                                                \
-    flash_bwd_dkv_kernel<DD, CC, true><<<gkv, blk, 0, stream>>>(                    \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,  \
-        SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],   \
-        kstr[1],                                                              \
-        kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],     \
-        kv_lo, kv_hi);                                                        \
-    if (small)                                                                \
-      flash_bwd_dq_kernel<DD, CC, 1, true><<<gq, blk, 0, stream>>>(                 \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
-          kv_lo, kv_hi);                                                      \
-    else                                                                      \
-      flash_bwd_dq_kernel<DD, CC, 2, true><<<gq, blk, 0, stream>>>(                 \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, SQ, SKV, B, HQ,  \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
-          kv_lo, kv_hi);                                                      \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASE(128, true); else CASE(128, false);
-  } else if (D == 64) {
-    if (causal) CASE(64, true); else CASE(64, false);
-  }
-#undef CASE
-}
-
-// same grids as launch_flash_bwd, SEGMENTED instantiations (causal,
-// S_q == S_kv == S): q_start / k_end are device int32 [B, S], non-decreasing
-// along each row, with 0 <= q_start[b,i] <= i < k_end[b,i] <= S
-void launch_flash_bwd_seg(const void* dout, const void* q, const void* k,
-                      const void* v, const void* lse, const void* delta,
-                      void* dq, void* dk, void* dv, int B, int HQ, int HKV,
-                      int S, int D, float scale, int window,
-                      const long* qstr, const long* kstr, const long* vstr,
-                      const long* dostr, const int* q_start, const int* k_end,
-                      bool pipe, hipStream_t stream) {
-  if (pipe)
-    launch_flash_dkv_pipe(dout, q, k, v, lse, delta, dk, dv, B, HQ, HKV, S, S,
-                          D, true, scale, window, qstr, kstr, vstr, dostr, 2,
-                          q_start, k_end, stream);
-  dim3 blk(512);
-  dim3 gkv((S + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
-  const bool small = ((long)((S + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 gq((S + bm - 1) / bm, B * HQ);
-#define CASE(DD)                                                              \
-  do {                                                                        \
-    if (!pipe)                                                                \
-    flash_bwd_dkv_kernel<DD, true, false, true><<<gkv, blk, 0, stream>>>(     \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, S,   \
-        S, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],     \
-        kstr[1],                                                              \
-        kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],     \
-        q_start, k_end);                                                      \
-    if (small)                                                                \
-      flash_bwd_dq_kernel<DD, true, 1, false, true>                           \
-          <<<gq, blk, 0, stream>>>(                                           \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, S, S, B, HQ,     \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
-          q_start, k_end);                                                    \
-    else                                                                      \
-      flash_bwd_dq_kernel<DD, true, 2, false, true>                           \
-          <<<gq, blk, 0, stream>>>(                                           \
-          (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,  \
-          (const float*)lse, (const float*)delta, (bf16*)dq, S, S, B, HQ,     \
-          HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1],    \
-          kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2],   \
-          q_start, k_end);                                                    \
-  } while (0)
-  if (D == 128) CASE(128);
-  else if (D == 64) CASE(64);
-#undef CASE
+  const int bm = flash_block_rows(a.SQ, a.B * a.HQ);
+  const dim3 gq((a.SQ + bm - 1) / bm, a.B * a.HQ);
+  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+    constexpr int D = decltype(d)::value;
+    constexpr bool C = decltype(c)::value, R = decltype(r)::value,
+                   S = decltype(s)::value;
+    auto kern = bm == 128 ? flash_bwd_dq_kernel<D, C, 1, R, S>
+                          : flash_bwd_dq_kernel<D, C, 2, R, S>;
+    kern<<<gq, blk, 0, stream>>>(
+        (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
+        (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta,
+        (bf16*)a.dq, a.SQ, a.SKV, a.B, a.HQ, a.HKV, a.scale, a.window,
+        a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0],
+        a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2], a.bound_a, a.bound_b);
+  });
 }
 }

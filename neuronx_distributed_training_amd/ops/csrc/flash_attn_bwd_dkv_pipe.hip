@@ -29,6 +29,7 @@
 // The q / dout sequence stride must satisfy 64 * stride * 2 B < 4 GiB (the
 // binding checks it).
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 template <int D, bool CAUSAL, bool RANGED = false, bool SEGMENTED = false>
 __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
@@ -393,38 +394,19 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
   }
 }
 
-extern "C" {
-// dK/dV only, same grid as the parent's launchers. mode 0: dense, 1: RANGED
-// (kv_lo / kv_hi int32 [B]), 2: SEGMENTED (q_start / k_end int32 [B, S],
-// causal, SQ == SKV).
-void launch_flash_dkv_pipe(const void* dout, const void* q, const void* k,
-                           const void* v, const void* lse, const void* delta,
-                           void* dk, void* dv, int B, int HQ, int HKV, int SQ,
-                           int SKV, int D, bool causal, float scale,
-                           int window, const long* qstr, const long* kstr,
-                           const long* vstr, const long* dostr, int mode,
-                           const int* bound_a, const int* bound_b,
-                           hipStream_t stream) {
-  dim3 blk(512);
-  dim3 gkv((SKV + 255) / 256, B * HQ);  // one block per (kblock, b, hkv, g)
-#define CASE(DD, CC, RR, SS)                                                  \
-  flash_bwd_dkv_pipe_kernel<DD, CC, RR, SS><<<gkv, blk, 0, stream>>>(         \
-      (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,      \
-      (const float*)lse, (const float*)delta, (float*)dk, (float*)dv, SQ,    \
-      SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],     \
-      kstr[1], kstr[2], vstr[0], vstr[1], vstr[2], dostr[0], dostr[1],        \
-      dostr[2], bound_a, bound_b)
-#define CASE_D(DD)                                                            \
-  do {                                                                        \
-    if (mode == 2) CASE(DD, true, false, true);                               \
-    else if (mode == 1 && causal) CASE(DD, true, true, false);                \
-    else if (mode == 1) CASE(DD, false, true, false);                         \
-    else if (causal) CASE(DD, true, false, false);                            \
-    else CASE(DD, false, false, false);                                       \
-  } while (0)
-  if (D == 128) CASE_D(128);
-  else if (D == 64) CASE_D(64);
-#undef CASE_D
-#undef CASE
-}
+// dK/dV only, same grid as the parent's launch in launch_flash_bwd
+extern "C" void launch_flash_dkv_pipe(const FlashArgs& a, hipStream_t stream) {
+  // one block per (kblock, b, hkv, g)
+  const dim3 gkv((a.SKV + 255) / 256, a.B * a.HQ), blk(512);
+  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+    flash_bwd_dkv_pipe_kernel<decltype(d)::value, decltype(c)::value,
+                              decltype(r)::value, decltype(s)::value>
+        <<<gkv, blk, 0, stream>>>(
+            (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
+            (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta,
+            (float*)a.dk, (float*)a.dv, a.SQ, a.SKV, a.B, a.HQ, a.HKV,
+            a.scale, a.window, a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1],
+            a.ks[2], a.vs[0], a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2],
+            a.bound_a, a.bound_b);
+  });
 }

@@ -16,6 +16,7 @@
 //   it into separate dV and dK kernels (S recompute is cheaper than the
 //   spill) before A/B-ing against v2.
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
@@ -377,40 +378,22 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_v3_kernel(
   }
 }
 
-extern "C" {
-void launch_flash_bwd_v3(const void* dout, const void* q, const void* k,
-                         const void* v, const void* lse, const void* delta,
-                         void* dq, void* dk, void* dv, int B, int HQ,
-                         int HKV, int S, int D, bool causal, float scale,
-                         int window, const long* qstr, const long* kstr,
-                         const long* vstr, const long* dostr,
-                         hipStream_t stream) {
-  dim3 blk(512);
-  dim3 gkv((S + 255) / 256, B * HQ);
-  dim3 gq((S + 255) / 256, B * HQ);
-#define CASEB3(DD, CC)                                                        \
-  do {                                                                        \
-    flash_bwd_dkv_v3_kernel<DD, CC, 0><<<gkv, blk, 0, stream>>>(              \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (float*)dv, S, B, HQ, HKV,    \
-        scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1], kstr[2],  \
-        vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);             \
-    flash_bwd_dkv_v3_kernel<DD, CC, 1><<<gkv, blk, 0, stream>>>(              \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (float*)dk, S, B, HQ, HKV,    \
-        scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1], kstr[2],  \
-        vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);             \
-    flash_bwd_dq_v3_kernel<DD, CC><<<gq, blk, 0, stream>>>(                   \
-        (const bf16*)dout, (const bf16*)q, (const bf16*)k, (const bf16*)v,    \
-        (const float*)lse, (const float*)delta, (bf16*)dq, S, B, HQ, HKV,     \
-        scale, window, qstr[0], qstr[1], qstr[2], kstr[0], kstr[1], kstr[2],  \
-        vstr[0], vstr[1], vstr[2], dostr[0], dostr[1], dostr[2]);             \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASEB3(128, true); else CASEB3(128, false);
-  } else if (D == 64) {
-    if (causal) CASEB3(64, true); else CASEB3(64, false);
-  }
-#undef CASEB3
-}
+extern "C" void launch_flash_bwd_v3(const FlashArgs& a, hipStream_t stream) {
+  const dim3 grid((a.SQ + 255) / 256, a.B * a.HQ), blk(512);
+  dispatch_dense(a, [&](auto d, auto c) {
+    constexpr int D = decltype(d)::value;
+    constexpr bool C = decltype(c)::value;
+    // dV, dK and dQ share one argument list but for the output
+    auto run = [&](auto kern, auto* out) {
+      kern<<<grid, blk, 0, stream>>>(
+          (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
+          (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta, out,
+          a.SQ, a.B, a.HQ, a.HKV, a.scale, a.window, a.qs[0], a.qs[1],
+          a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0], a.vs[1], a.vs[2],
+          a.ds[0], a.ds[1], a.ds[2]);
+    };
+    run(flash_bwd_dkv_v3_kernel<D, C, 0>, (float*)a.dv);
+    run(flash_bwd_dkv_v3_kernel<D, C, 1>, (float*)a.dk);
+    run(flash_bwd_dq_v3_kernel<D, C>, (bf16*)a.dq);
+  });
 }

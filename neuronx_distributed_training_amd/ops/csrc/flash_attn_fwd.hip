@@ -12,6 +12,7 @@
 //  - V^T staged with paired bf16x2 writes (half the ds_write count).
 //  - LDS ≈ 73 KB → 2 blocks/CU → 4 waves/SIMD.
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 // NSB = 16-row sub-blocks per wave: 2 -> BM 256 (the TP<=4 shape), 1 ->
 // BM 128 for small B*HQ launches (TP=8 has HQ_local=4: BM=256 gives 256
@@ -323,35 +324,17 @@ __global__ __launch_bounds__(512) void flash_fwd_kernel(
   }
 }
 
-extern "C" {
-void launch_flash_fwd(const void* q, const void* k, const void* v, void* o,
-                      void* lse, int B, int HQ, int HKV, int SQ, int SKV,
-                      int D, bool causal, float scale, int window,
-                      const long* qstr, const long* kstr, const long* vstr,
-                      hipStream_t stream) {
-  // BM=128 when the BM=256 grid would leave CUs idle (TP=8: HQ_local=4)
-  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 grid((SQ + bm - 1) / bm, B * HQ);
-  dim3 blk(512);
-#define CASE(DD, CC)                                                          \
-  do {                                                                        \
-    if (small)                                                                \
-      flash_fwd_kernel<DD, CC, 1><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2]);     \
-    else                                                                      \
-      flash_fwd_kernel<DD, CC, 2><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2]);     \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASE(128, true); else CASE(128, false);
-  } else if (D == 64) {
-    if (causal) CASE(64, true); else CASE(64, false);
-  }
-#undef CASE
-}
+extern "C" void launch_flash_fwd(const FlashArgs& a, hipStream_t stream) {
+  const int bm = flash_block_rows(a.SQ, a.B * a.HQ);
+  const dim3 grid((a.SQ + bm - 1) / bm, a.B * a.HQ), blk(512);
+  dispatch_dense(a, [&](auto d, auto c) {
+    constexpr int D = decltype(d)::value;
+    constexpr bool C = decltype(c)::value;
+    auto kern = bm == 128 ? flash_fwd_kernel<D, C, 1> : flash_fwd_kernel<D, C, 2>;
+    kern<<<grid, blk, 0, stream>>>(
+        (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (bf16*)a.o,
+        (float*)a.lse, a.SQ, a.SKV, a.B, a.HQ, a.HKV, a.scale, a.window,
+        a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0],
+        a.vs[1], a.vs[2]);
+  });
 }

@@ -1,9 +1,11 @@
-// DOUBLE-BUFFERED variant of flash_fwd_kernel (dark; A/B via the
-// flash_attn_fwd_dbuf binding): two K/V LDS buffer sets -> ONE barrier
+// DOUBLE-BUFFERED variant of flash_fwd_kernel, the default forward (the
+// single-buffered kernel stays reachable for A/B as the flash_attn_fwd_sbuf
+// binding; bit-identical output): two K/V LDS buffer sets -> ONE barrier
 // per tile and the staging writes overlap the previous tile's MFMAs.
-// LDS 108.5 KB -> 1 block/CU (8 waves) vs the default's 2 blocks; which
-// side wins is an empirical question (the dkv kernel lives at 1 block).
+// LDS 108.5 KB -> 1 block/CU (8 waves) vs the single-buffered kernel's 2
+// blocks; measured +3.0% (bench shape) / +1.8% (TP=8 shape).
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 // NSB = 16-row sub-blocks per wave: 2 -> BM 256 (the TP<=4 shape), 1 ->
 // BM 128 for small B*HQ launches (TP=8 has HQ_local=4: BM=256 gives 256
@@ -399,105 +401,19 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
   }
 }
 
-extern "C" {
-void launch_flash_fwd_dbuf(const void* q, const void* k, const void* v, void* o,
-                      void* lse, int B, int HQ, int HKV, int SQ, int SKV,
-                      int D, bool causal, float scale, int window,
-                      const long* qstr, const long* kstr, const long* vstr,
-                      hipStream_t stream) {
-  // BM=128 when the BM=256 grid would leave CUs idle (TP=8: HQ_local=4)
-  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 grid((SQ + bm - 1) / bm, B * HQ);
-  dim3 blk(512);
-#define CASE(DD, CC)                                                          \
-  do {                                                                        \
-    if (small)                                                                \
-      flash_fwd_dbuf_kernel<DD, CC, 1><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2]);     \
-    else                                                                      \
-      flash_fwd_dbuf_kernel<DD, CC, 2><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2]);     \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASE(128, true); else CASE(128, false);
-  } else if (D == 64) {
-    if (causal) CASE(64, true); else CASE(64, false);
-  }
-#undef CASE
-}
-
-// same tiling rule as launch_flash_fwd_dbuf, RANGED instantiations:
-// kv_lo / kv_hi are device int32 [B] with 0 <= lo <= hi <= SKV
-void launch_flash_fwd_range(const void* q, const void* k, const void* v, void* o,
-                      void* lse, int B, int HQ, int HKV, int SQ, int SKV,
-                      int D, bool causal, float scale, int window,
-                      const long* qstr, const long* kstr, const long* vstr,
-                      const int* kv_lo, const int* kv_hi,
-                      hipStream_t stream) {
-  // BM=128 when the BM=256 grid would leave CUs idle (TP=8: HQ_local=4)
-  const bool small = ((long)((SQ + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 grid((SQ + bm - 1) / bm, B * HQ);
-  dim3 blk(512);
-#define CASE(DD, CC)                                                          \
-  do {                                                                        \
-    if (small)                                                                \
-      flash_fwd_dbuf_kernel<DD, CC, 1, true><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
-          kv_lo, kv_hi);                                                      \
-    else                                                                      \
-      flash_fwd_dbuf_kernel<DD, CC, 2, true><<<grid, blk, 0, stream>>>(                  \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, SQ, SKV, B, HQ, HKV, scale, window, qstr[0], qstr[1],  \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
-          kv_lo, kv_hi);                                                      \
-  } while (0)
-  if (D == 128) {
-    if (causal) CASE(128, true); else CASE(128, false);
-  } else if (D == 64) {
-    if (causal) CASE(64, true); else CASE(64, false);
-  }
-#undef CASE
-}
-
-// SEGMENTED instantiations (causal, S_q == S_kv == S): q_start / k_end are
-// device int32 [B, S], non-decreasing along each row, with
-// 0 <= q_start[b,i] <= i < k_end[b,i] <= S. Same tiling rule as above.
-void launch_flash_fwd_seg(const void* q, const void* k, const void* v, void* o,
-                      void* lse, int B, int HQ, int HKV, int S, int D,
-                      float scale, int window, const long* qstr,
-                      const long* kstr, const long* vstr, const int* q_start,
-                      const int* k_end, hipStream_t stream) {
-  const bool small = ((long)((S + 255) / 256) * B * HQ) < 512;
-  const int bm = small ? 128 : 256;
-  dim3 grid((S + bm - 1) / bm, B * HQ);
-  dim3 blk(512);
-#define CASE(DD)                                                              \
-  do {                                                                        \
-    if (small)                                                                \
-      flash_fwd_dbuf_kernel<DD, true, 1, false, true>                         \
-          <<<grid, blk, 0, stream>>>(                                         \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, S, S, B, HQ, HKV, scale, window, qstr[0], qstr[1],     \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
-          q_start, k_end);                                                    \
-    else                                                                      \
-      flash_fwd_dbuf_kernel<DD, true, 2, false, true>                         \
-          <<<grid, blk, 0, stream>>>(                                         \
-          (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o,           \
-          (float*)lse, S, S, B, HQ, HKV, scale, window, qstr[0], qstr[1],     \
-          qstr[2], kstr[0], kstr[1], kstr[2], vstr[0], vstr[1], vstr[2],      \
-          q_start, k_end);                                                    \
-  } while (0)
-  if (D == 128) CASE(128);
-  else if (D == 64) CASE(64);
-#undef CASE
-}
+extern "C" void launch_flash_fwd_dbuf(const FlashArgs& a, hipStream_t stream) {
+  const int bm = flash_block_rows(a.SQ, a.B * a.HQ);
+  const dim3 grid((a.SQ + bm - 1) / bm, a.B * a.HQ), blk(512);
+  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+    constexpr int D = decltype(d)::value;
+    constexpr bool C = decltype(c)::value, R = decltype(r)::value,
+                   S = decltype(s)::value;
+    auto kern = bm == 128 ? flash_fwd_dbuf_kernel<D, C, 1, R, S>
+                          : flash_fwd_dbuf_kernel<D, C, 2, R, S>;
+    kern<<<grid, blk, 0, stream>>>(
+        (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (bf16*)a.o,
+        (float*)a.lse, a.SQ, a.SKV, a.B, a.HQ, a.HKV, a.scale, a.window,
+        a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0],
+        a.vs[1], a.vs[2], a.bound_a, a.bound_b);
+  });
 }

@@ -14,6 +14,7 @@
 // Geometry: 8 waves × 32 queries = BM 256; BN = 32 keys/tile staged in
 // LDS (K row-major + V^T with the tr_swz XOR swizzle).
 #include "attn_common.h"
+#include "flash_dispatch.h"
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
@@ -271,24 +272,14 @@ __global__ __launch_bounds__(512) void flash_fwd_v3_kernel(
   }
 }
 
-extern "C" {
-void launch_flash_fwd_v3(const void* q, const void* k, const void* v, void* o,
-                         void* lse, int B, int HQ, int HKV, int S, int D,
-                         bool causal, float scale, int window,
-                         const long* qstr, const long* kstr, const long* vstr,
-                         hipStream_t stream) {
-  dim3 grid((S + 255) / 256, B * HQ);
-  dim3 blk(512);
-#define CASEV3(DD, CC)                                                        \
-  flash_fwd_v3_kernel<DD, CC><<<grid, blk, 0, stream>>>(                      \
-      (const bf16*)q, (const bf16*)k, (const bf16*)v, (bf16*)o, (float*)lse, \
-      S, B, HQ, HKV, scale, window, qstr[0], qstr[1], qstr[2], kstr[0],       \
-      kstr[1], kstr[2], vstr[0], vstr[1], vstr[2])
-  if (D == 128) {
-    if (causal) CASEV3(128, true); else CASEV3(128, false);
-  } else if (D == 64) {
-    if (causal) CASEV3(64, true); else CASEV3(64, false);
-  }
-#undef CASEV3
-}
+extern "C" void launch_flash_fwd_v3(const FlashArgs& a, hipStream_t stream) {
+  const dim3 grid((a.SQ + 255) / 256, a.B * a.HQ), blk(512);
+  dispatch_dense(a, [&](auto d, auto c) {
+    flash_fwd_v3_kernel<decltype(d)::value, decltype(c)::value>
+        <<<grid, blk, 0, stream>>>(
+            (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (bf16*)a.o,
+            (float*)a.lse, a.SQ, a.B, a.HQ, a.HKV, a.scale, a.window, a.qs[0],
+            a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0], a.vs[1],
+            a.vs[2]);
+  });
 }

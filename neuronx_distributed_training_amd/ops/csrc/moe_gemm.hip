@@ -18,6 +18,7 @@
 // each wave owns 32 output rows (2 sub-blocks of 16) x BN cols;
 // 16x16x32 bf16 MFMA; operands staged through LDS per BK chunk.
 #include "attn_common.h"
+#include "launch.h"
 
 // ============================ fwd / dgrad ============================
 // TRANS_B = false: contraction over W's LAST dim (fwd, x @ W^T):

@@ -3,6 +3,7 @@
 // torch.matmul — a failure means the lane→element maps are wrong and every
 // attention kernel is too (asymmetric B catches transposes).
 #include "attn_common.h"
+#include "launch.h"
 
 __global__ void mfma_probe_kernel(const bf16* __restrict__ A,
                                   const bf16* __restrict__ B,

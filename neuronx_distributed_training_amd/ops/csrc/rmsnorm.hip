@@ -3,6 +3,7 @@
 // bf16 IO, fp32 accumulate; vectorized 8×bf16 (16 B) loads per lane
 // (guide: scalar bf16 loads are a 2× loss on this op).
 #include "common.h"
+#include "launch.h"
 
 // ---------------- forward ----------------
 // x: [N, H] bf16, w: [H] bf16 -> y: [N, H] bf16, invrms: [N] f32.

@@ -4,6 +4,7 @@
 // attention path does zero permute/contiguous copies.
 // cos/sin tables [Smax, D] fp32; backward = forward with -sin (orthogonal).
 #include "common.h"
+#include "launch.h"
 
 __global__ void rope_fwd_kernel(const bf16* __restrict__ x,
                                 const float* __restrict__ cost,

@@ -1,6 +1,7 @@
 // Fused SwiGLU fwd/bwd: y = silu(gate) * up with gate_up packed
 // [N, 2I] = [gate | up] (fused ColumnParallel output). One HBM pass.
 #include "common.h"
+#include "launch.h"
 
 __global__ void swiglu_fwd_kernel(const bf16* __restrict__ gu,
                                   bf16* __restrict__ y, long N, int I) {
