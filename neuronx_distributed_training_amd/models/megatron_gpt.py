@@ -35,6 +35,7 @@ from ..parallel.mappings import (
 )
 from ..modules.moe import ExpertMLPs, MoE, RouterSinkhorn, RouterTopK, load_balancing_loss_func
 from ..ops import flash_attn_func, swiglu
+from ..ops.flash_attn import draw_dropout_rng
 from ..ops.rmsnorm import RMSNorm
 from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
 
@@ -224,8 +225,17 @@ class ParallelAttention(nn.Module):
             dtype=cfg.torch_dtype, init_seed=seed + 2,
         )
         self.attn_dropout_p = cfg.attention_dropout
+        if (self.attn_dropout_p > 0
+                and ps.get_context_model_parallel_world_size() > 1):
+            raise ValueError(
+                "attention_dropout > 0 is not supported with "
+                "context_parallel_size > 1 (ring attention has no dropout); "
+                "set model.attention_dropout to 0 or disable CP"
+            )
 
-    def core_attention(self, q, k, v):
+    def core_attention(self, q, k, v, dropout_rng=None):
+        """dropout_rng: the (seed, offset) pair of this call's attention
+        dropout, or None for no dropout (eval mode, attention_dropout 0)."""
         if ps.get_context_model_parallel_world_size() > 1:
             from ..ops.ring_attn import ring_flash_attn
 
@@ -235,10 +245,25 @@ class ParallelAttention(nn.Module):
                 "causal attention); disable CP or the window"
             )
             return ring_flash_attn(q, k, v, scale=self.scale)
-        return flash_attn_func(q, k, v, causal=True, scale=self.scale,
-                               window=self.cfg.sliding_window)
+        return flash_attn_func(
+            q, k, v, causal=True, scale=self.scale,
+            window=self.cfg.sliding_window,
+            dropout_p=self.attn_dropout_p if dropout_rng is not None else 0.0,
+            dropout_rng=dropout_rng,
+        )
 
-    def forward(self, x, cos, sin, pos_offset=0):
+    def draw_attn_dropout_rng(self, device):
+        """The (seed, offset) pair of one forward's attention dropout, or
+        None when none applies (eval mode, attention_dropout 0). Attention
+        dropout acts on TP-sharded heads, so the pair is drawn per rank
+        under the tracker's fork, like the reference's nn.Dropout in
+        CoreAttention."""
+        if not (self.training and self.attn_dropout_p > 0):
+            return None
+        with get_rng_tracker().fork():
+            return draw_dropout_rng(device)
+
+    def forward(self, x, cos, sin, pos_offset=0, attn_dropout_rng=None):
         s_in, b = x.size(0), x.size(1)
         d = self.head_dim
         if hasattr(self, "query_key_value"):
@@ -264,10 +289,19 @@ class ParallelAttention(nn.Module):
         if cos is not None:
             q = apply_rotary_pos_emb(q, cos, sin, pos_offset)
             k = apply_rotary_pos_emb(k, cos, sin, pos_offset)
+        # The pair is drawn OUTSIDE every checkpointed function (here for
+        # selective checkpointing; by GPTModel.forward, which hands it in,
+        # for full): a draw inside one would see the tracker's advanced state
+        # on recompute, and the backward would pair a recomputed O of one
+        # mask with the saved pair of another.
+        dropout_rng = attn_dropout_rng
+        if dropout_rng is None:
+            dropout_rng = self.draw_attn_dropout_rng(q.device)
         if self.cfg.activation_checkpoint == "selective" and self.training:
-            o = _ckpt(self.core_attention, q, k, v, use_reentrant=False)
+            o = _ckpt(self.core_attention, q, k, v, dropout_rng,
+                      use_reentrant=False)
         else:
-            o = self.core_attention(q, k, v)
+            o = self.core_attention(q, k, v, dropout_rng)
         o = o.permute(2, 0, 1, 3).reshape(s, b, self.n_heads_local * d)
         return self.dense(o)
 
@@ -303,21 +337,23 @@ class ParallelTransformerLayer(nn.Module):
             return self.mlp(h)
         return self.mlp(h), None
 
-    def forward(self, x, cos, sin, pos_offset=0):
+    def forward(self, x, cos, sin, pos_offset=0, attn_dropout_rng=None):
         if self.block_type == "post_ln":
-            a = self.self_attention(x, cos, sin, pos_offset)
+            a = self.self_attention(x, cos, sin, pos_offset, attn_dropout_rng)
             x = self.input_layernorm(x + self._drop(a))
             m, logits = self._mlp(x)
             x = self.post_attention_layernorm(x + self._drop(m))
         elif self.block_type == "normformer":
             # extra norm on the attention output before the residual add
             # (reference transformer.py normformer block type)
-            a = self.self_attention(self.input_layernorm(x), cos, sin, pos_offset)
+            a = self.self_attention(self.input_layernorm(x), cos, sin,
+                                    pos_offset, attn_dropout_rng)
             x = x + self._drop(self.post_inner_layernorm(a))
             m, logits = self._mlp(self.post_attention_layernorm(x))
             x = x + self._drop(m)
         else:  # pre_ln
-            a = self.self_attention(self.input_layernorm(x), cos, sin, pos_offset)
+            a = self.self_attention(self.input_layernorm(x), cos, sin,
+                                    pos_offset, attn_dropout_rng)
             x = x + self._drop(a)
             m, logits = self._mlp(self.post_attention_layernorm(x))
             x = x + self._drop(m)
@@ -408,8 +444,11 @@ class GPTModel(nn.Module):
         full_ckpt = self.cfg.activation_checkpoint == "full" and self.training
         for layer in self.layers:
             if full_ckpt:
+                # the layer's attention-dropout pair is drawn out here, so
+                # that the recompute regenerates the same mask
+                rng = layer.self_attention.draw_attn_dropout_rng(x.device)
                 x, lg = _ckpt(layer, x, self.rope_cos, self.rope_sin, pos_offset,
-                              use_reentrant=False)
+                              rng, use_reentrant=False)
             else:
                 x, lg = layer(x, self.rope_cos, self.rope_sin, pos_offset)
             if lg is not None:

@@ -9,7 +9,9 @@ Every op has two paths:
 
 Kernel inventory (replacing the reference's NKI/apex device stack, SURVEY.md
 §2.3): rmsnorm fwd/bwd, rope fwd/bwd, swiglu fwd/bwd, flash attention
-fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax), vocab-parallel CE
+fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
+sequences, and attention dropout regenerated in-kernel from a counter-based
+keep mask, with a stand-alone mask kernel for tests), vocab-parallel CE
 statistics, fused AdamW(fp32 state).
 """
 
@@ -79,6 +81,8 @@ from .rmsnorm import rmsnorm  # noqa: E402
 from .rope import apply_rotary_pos_emb  # noqa: E402
 from .swiglu import swiglu  # noqa: E402
 from .flash_attn import (  # noqa: E402
+    dropout_keep_mask,
+    dropout_keep_scale,
     flash_attn_func,
     mask_to_kv_range,
     segment_bounds,
@@ -92,6 +96,8 @@ __all__ = [
     "apply_rotary_pos_emb",
     "swiglu",
     "flash_attn_func",
+    "dropout_keep_mask",
+    "dropout_keep_scale",
     "mask_to_kv_range",
     "segment_bounds",
 ]

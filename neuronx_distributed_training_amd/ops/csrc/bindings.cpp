@@ -1,6 +1,9 @@
 // PyTorch bindings for the MI355X HIP kernels (gfx950-only build).
 #include <torch/extension.h>
 
+#include <cmath>
+#include <cstdint>
+
 #include <hip/hip_runtime.h>
 
 #include <c10/hip/HIPStream.h>
@@ -243,6 +246,25 @@ static void set_mask(FlashArgs& a, FlashArgs::Mask mask,
   }
 }
 
+// Attention dropout: p_drop in [0, 1) -> 8-bit threshold t = round(256 * p)
+// (an element is dropped iff its random byte is < t; 0 = no dropout). A p
+// that rounds to 256 would drop everything and is rejected with the rest.
+static int drop_threshold(double p_drop) {
+  TORCH_CHECK(p_drop >= 0.0 && p_drop < 1.0,
+              "p_drop must be in [0, 1), got ", p_drop);
+  const long t = std::lround(256.0 * p_drop);
+  TORCH_CHECK(t <= 255, "p_drop ", p_drop,
+              " rounds to 256/256: the threshold has 8 bits");
+  return (int)t;
+}
+
+static void set_dropout(FlashArgs& a, double p_drop, uint64_t seed,
+                        uint64_t offset) {
+  a.drop_t = drop_threshold(p_drop);
+  a.drop_seed = seed;
+  a.drop_offset = offset;
+}
+
 static torch::Tensor attn_delta(torch::Tensor dout, torch::Tensor o) {
   // fused rowsum(dO . O) -> [B, HQ, SQ] fp32 (no fp32 materialization)
   auto oc = o.stride(3) == 1 ? o : o.contiguous();
@@ -350,10 +372,13 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
 // Values are trusted to be non-decreasing along each row with
 // 0 <= q_start[b,i] <= i < k_end[b,i] <= S; the Python op derives them from
 // segment ids.
+// p_drop (non-null only from flash_attn_fwd_drop, DENSE): attention dropout
+// on the probabilities with the keep mask of stream (seed, offset).
 static std::vector<torch::Tensor> flash_fwd_common(
     bool dbuf, FlashArgs::Mask mask, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, const torch::Tensor* lo, const torch::Tensor* hi,
-    bool causal, double scale, long window) {
+    bool causal, double scale, long window, const double* p_drop = nullptr,
+    uint64_t seed = 0, uint64_t offset = 0) {
   check_bhsd(q, "q");
   check_bhsd(k, "k");
   check_bhsd(v, "v");
@@ -372,6 +397,7 @@ static std::vector<torch::Tensor> flash_fwd_common(
   if (mask != FlashArgs::SEGMENTED)
     TORCH_CHECK(!causal || a.SKV >= a.SQ, "causal needs S_kv >= S_q");
   set_mask(a, mask, lo, hi);
+  if (p_drop) set_dropout(a, *p_drop, seed, offset);
   return flash_fwd_run(a, q,
                        dbuf ? launch_flash_fwd_dbuf : launch_flash_fwd);
 }
@@ -405,6 +431,40 @@ std::vector<torch::Tensor> flash_attn_fwd_seg(
                           &k_end, true, scale, window);
 }
 
+// Dense attention with dropout on the probabilities: O = ((P . M) V) *
+// keep_scale with the keep mask M of flash_attn_dropout_mask(.., p_drop,
+// seed, offset); LSE is that of the undropped softmax. t == 0 (p_drop below
+// 1/512) is the dense kernel.
+std::vector<torch::Tensor> flash_attn_fwd_drop(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    double scale, long window, double p_drop, uint64_t seed,
+    uint64_t offset) {
+  return flash_fwd_common(true, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
+                          causal, scale, window, &p_drop, seed, offset);
+}
+
+// The keep mask of (p_drop, seed, offset) as uint8 [B, HQ, SQ, SKV] on the
+// current device, 1 = keep: test and debug support, on no hot path.
+torch::Tensor flash_attn_dropout_mask(long B, long HQ, long SQ, long SKV,
+                                      double p_drop, uint64_t seed,
+                                      uint64_t offset) {
+  const int t = drop_threshold(p_drop);
+  TORCH_CHECK(B >= 0 && HQ >= 0 && SQ >= 0 && SKV >= 0,
+              "dropout mask: negative size");
+  TORCH_CHECK(B * HQ < (1L << 31) && SQ < (1L << 31) && SKV < (1L << 31),
+              "dropout mask: B * HQ, SQ and SKV must be below 2^31");
+  // one thread per element, 256 per block, grid.x < 2^31
+  TORCH_CHECK((double)B * HQ * SQ * SKV < 256.0 * 2147483647.0,
+              "dropout mask: too many elements");
+  auto mask = torch::empty(
+      {B, HQ, SQ, SKV},
+      torch::TensorOptions().dtype(torch::kUInt8).device(
+          torch::kCUDA, c10::hip::current_device()));
+  launch_attn_dropout_mask(mask.data_ptr(), (int)B, (int)HQ, (int)SQ,
+                           (int)SKV, t, seed, offset, cur_stream());
+  return mask;
+}
+
 // Shared body of the six backward bindings; mask, lo and hi as in
 // flash_fwd_common. pipe selects the dK/dV kernel: true = the pipelined
 // kernel (flash_attn_bwd_dkv_pipe.hip, the default), false = the
@@ -414,7 +474,8 @@ static std::vector<torch::Tensor> flash_bwd_common(
     FlashArgs::Mask mask, bool pipe, torch::Tensor dout, torch::Tensor q,
     torch::Tensor k, torch::Tensor v, torch::Tensor o, torch::Tensor lse,
     const torch::Tensor* lo, const torch::Tensor* hi, bool causal,
-    double scale, long window) {
+    double scale, long window, const double* p_drop = nullptr,
+    uint64_t seed = 0, uint64_t offset = 0) {
   if (dout.stride(3) != 1) dout = dout.contiguous();
   check_bhsd(dout, "dout");
   check_bhsd(q, "q");
@@ -436,6 +497,7 @@ static std::vector<torch::Tensor> flash_bwd_common(
                         dout.stride(2) >= 0 && dout.stride(2) < (1L << 24)),
               "q / dout sequence stride must be below 2^24 elements");
   set_mask(a, mask, lo, hi);
+  if (p_drop) set_dropout(a, *p_drop, seed, offset);
   return flash_bwd_run(a, dout, q, o, lse,
                        [pipe](const FlashArgs& f, hipStream_t stream) {
                          launch_flash_bwd(f, pipe, stream);
@@ -467,6 +529,18 @@ static std::vector<torch::Tensor> flash_bwd_common(
 BWD_BINDINGS(, true)        // pipelined dK/dV (default)
 BWD_BINDINGS(_sbuf, false)  // the kernel it replaced, for A/B
 #undef BWD_BINDINGS
+
+// Backward of flash_attn_fwd_drop: o and lse are its outputs, and (p_drop,
+// seed, offset) the values it was given; the kernels regenerate the mask.
+// dK/dV always come from the pipelined kernel.
+std::vector<torch::Tensor> flash_attn_bwd_drop(
+    torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
+    torch::Tensor o, torch::Tensor lse, bool causal, double scale,
+    long window, double p_drop, uint64_t seed, uint64_t offset) {
+  return flash_bwd_common(FlashArgs::DENSE, true, dout, q, k, v, o, lse,
+                          nullptr, nullptr, causal, scale, window, &p_drop,
+                          seed, offset);
+}
 
 torch::Tensor moe_gemm(torch::Tensor a, torch::Tensor w,
                        torch::Tensor tile_expert, torch::Tensor total_rows,
@@ -625,6 +699,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("q_start"),
         pybind11::arg("k_end"), pybind11::arg("scale"),
         pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_drop", &flash_attn_fwd_drop, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window"),
+        pybind11::arg("p_drop"), pybind11::arg("seed"),
+        pybind11::arg("offset"));
+  m.def("flash_attn_bwd_drop", &flash_attn_bwd_drop, pybind11::arg("dout"),
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window"),
+        pybind11::arg("p_drop"), pybind11::arg("seed"),
+        pybind11::arg("offset"));
+  m.def("flash_attn_dropout_mask", &flash_attn_dropout_mask,
+        pybind11::arg("B"), pybind11::arg("HQ"), pybind11::arg("SQ"),
+        pybind11::arg("SKV"), pybind11::arg("p_drop"), pybind11::arg("seed"),
+        pybind11::arg("offset"));
   m.def("flash_attn_bwd_sbuf", &flash_attn_bwd_sbuf, pybind11::arg("dout"),
         pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("causal"),

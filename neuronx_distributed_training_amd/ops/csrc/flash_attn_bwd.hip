@@ -10,6 +10,7 @@
 // writes. dkv: BN=256 keys (32/wave), q-tile 64. dq: BM=256 (32/wave),
 // key tile 64.
 #include "attn_common.h"
+#include "attn_dropout.h"
 #include "flash_dispatch.h"
 
 // RANGED (both kernels): per-batch-row visible key range
@@ -311,8 +312,13 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_kernel(
 // ============================ dQ ============================
 // NSB: 16-row sub-blocks per wave (see flash_fwd_kernel) — NSB=1 keeps
 // the chip full at TP=8's HQ_local=4
+//
+// DROPOUT (DENSE mask only): dS = P . (M * keep_scale . dP - delta) * scale
+// with the keep mask M of attn_dropout.h the forward used; LSE and delta
+// come from that forward. A lane's four words of a 64-key tile (one per
+// 16-key chunk) are generated once per tile and sub-block.
 template <int D, bool CAUSAL, int NSB, bool RANGED = false,
-          bool SEGMENTED = false>
+          bool SEGMENTED = false, bool DROPOUT = false>
 __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -322,9 +328,12 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     long sQs, long sQb, long sQh, long sKs, long sKb, long sKh, long sVs,
     long sVb, long sVh, long sDs, long sDb, long sDh,
     const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED), or
-    const int* __restrict__ kv_hi = nullptr) {  // [B, S] (SEGMENTED)
+    const int* __restrict__ kv_hi = nullptr,  // [B, S] (SEGMENTED)
+    int drop_t = 0,  // DROPOUT: threshold 1..255 and the random stream
+    unsigned long long drop_seed = 0, unsigned long long drop_off = 0) {
   static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
   static_assert(!SEGMENTED || CAUSAL, "segments are causal");
+  static_assert(!DROPOUT || !(RANGED || SEGMENTED), "dropout: DENSE only");
   constexpr int BM = NSB * 128, BN = 64;  // BN=32 (2 blk/CU) was slower
   const int coff = SKV - SQ;  // bottom-right causal alignment
   constexpr int KP = D + 8;
@@ -478,6 +487,18 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
     if ((!CAUSAL || kbase <= wrow_max + coff) &&
         (!SEGMENTED || kbase + BN > qs_wave)) {
       __bf16* dsw = &ds_lds[wid * NSB * 16 * VP];
+      // DROPOUT: word nk of a call is key kbase + nk * 16 + (lane & 15)
+      DropWords dw[NSB];
+      float kscale = 1.f;
+      if constexpr (DROPOUT) {
+        kscale = dropout_keep_scale(drop_t);
+#pragma unroll
+        for (int sb = 0; sb < NSB; ++sb)
+          dw[sb] = dropout_words(
+              drop_seed, drop_off, (uint)bh,
+              (uint)(qrow_w + sb * 16 + (lane >> 4) * 4) >> 2,
+              dropout_key_group(kbase + (lane & 15)));
+      }
 #pragma unroll
       for (int nk = 0; nk < BN / 16; ++nk) {
         f32x4_t st[NSB], dpt[NSB];
@@ -514,7 +535,11 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const float p = __expf(st[sb][r] - lse[sb][r]);
-              const float ds = p * (dpt[sb][r] - delta[sb][r]) * scale;
+              float dp = dpt[sb][r];
+              if constexpr (DROPOUT)
+                dp = dropout_keep_byte(dw[sb].w[nk], r, drop_t) ? dp * kscale
+                                                                : 0.f;
+              const float ds = p * (dp - delta[sb][r]) * scale;
               dsw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 +
                   (lane & 15)] = (__bf16)ds;
             }
@@ -531,7 +556,11 @@ __global__ __launch_bounds__(512) void flash_bwd_dq_kernel(
               if constexpr (RANGED) dead |= (kcol < lo) || (kcol >= hi);
               if constexpr (SEGMENTED) dead |= (kcol < qs[sb][r]);
               const float p = dead ? 0.f : __expf(st[sb][r] - lse[sb][r]);
-              const float ds = p * (dpt[sb][r] - delta[sb][r]) * scale;
+              float dp = dpt[sb][r];
+              if constexpr (DROPOUT)
+                dp = dropout_keep_byte(dw[sb].w[nk], r, drop_t) ? dp * kscale
+                                                                : 0.f;
+              const float ds = p * (dp - delta[sb][r]) * scale;
               dsw[(sb * 16 + (lane >> 4) * 4 + r) * VP + nk * 16 +
                   (lane & 15)] = (__bf16)ds;
             }
@@ -642,7 +671,9 @@ void launch_attn_delta(const void* dout, const void* o, void* delta, int SQ,
 // above, the A/B arm, bit-equal), then dQ, the same kernel in both.
 void launch_flash_bwd(const FlashArgs& a, bool pipe, hipStream_t stream) {
   const dim3 blk(512);
-  if (pipe) {
+  // the single-buffered dK/dV kernel has no dropout instantiation (its lanes
+  // hold one query x four keys, the transpose of the random words' footprint)
+  if (pipe || a.drop_t > 0) {
     launch_flash_dkv_pipe(a, stream);
   } else {
     // one block per (kblock, b, hkv, g)
@@ -661,18 +692,19 @@ void launch_flash_bwd(const FlashArgs& a, bool pipe, hipStream_t stream) {
   }
   const int bm = flash_block_rows(a.SQ, a.B * a.HQ);
   const dim3 gq((a.SQ + bm - 1) / bm, a.B * a.HQ);
-  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+  dispatch_flash_drop(a, [&](auto d, auto c, auto r, auto s, auto p) {
     constexpr int D = decltype(d)::value;
     constexpr bool C = decltype(c)::value, R = decltype(r)::value,
-                   S = decltype(s)::value;
-    auto kern = bm == 128 ? flash_bwd_dq_kernel<D, C, 1, R, S>
-                          : flash_bwd_dq_kernel<D, C, 2, R, S>;
+                   S = decltype(s)::value, P = decltype(p)::value;
+    auto kern = bm == 128 ? flash_bwd_dq_kernel<D, C, 1, R, S, P>
+                          : flash_bwd_dq_kernel<D, C, 2, R, S, P>;
     kern<<<gq, blk, 0, stream>>>(
         (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
         (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta,
         (bf16*)a.dq, a.SQ, a.SKV, a.B, a.HQ, a.HKV, a.scale, a.window,
         a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0],
-        a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2], a.bound_a, a.bound_b);
+        a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2], a.bound_a, a.bound_b,
+        a.drop_t, a.drop_seed, a.drop_offset);
   });
 }
 }

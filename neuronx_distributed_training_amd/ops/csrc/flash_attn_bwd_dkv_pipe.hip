@@ -28,10 +28,20 @@
 //
 // The q / dout sequence stride must satisfy 64 * stride * 2 B < 4 GiB (the
 // binding checks it).
+//
+// DROPOUT (DENSE mask only; no counterpart in the parent kernel):
+// dV = (P . M * keep_scale)^T dO and dS = P . (M * keep_scale . dP - delta)
+// * scale with the keep mask M of attn_dropout.h. By point 5 a lane holds
+// four consecutive queries at key l15 of both 16-key strips, i.e. two of the
+// four words of one call (the wave's 32 keys are half a 64-key block). The
+// words are generated per 16-query sub-tile, after the MFMAs, and are dead
+// before the next one.
 #include "attn_common.h"
+#include "attn_dropout.h"
 #include "flash_dispatch.h"
 
-template <int D, bool CAUSAL, bool RANGED = false, bool SEGMENTED = false>
+template <int D, bool CAUSAL, bool RANGED = false, bool SEGMENTED = false,
+          bool DROPOUT = false>
 __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
     const bf16* __restrict__ dO, const bf16* __restrict__ Q,
     const bf16* __restrict__ K, const bf16* __restrict__ V,
@@ -42,9 +52,12 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
     int window, long sQs, long sQb, long sQh, long sKs, long sKb, long sKh,
     long sVs, long sVb, long sVh, long sDs, long sDb, long sDh,
     const int* __restrict__ kv_lo = nullptr,  // [B] int32 (RANGED), or
-    const int* __restrict__ kv_hi = nullptr) {  // [B, S] (SEGMENTED)
+    const int* __restrict__ kv_hi = nullptr,  // [B, S] (SEGMENTED)
+    int drop_t = 0,  // DROPOUT: threshold 1..255 and the random stream
+    unsigned long long drop_seed = 0, unsigned long long drop_off = 0) {
   static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
   static_assert(!SEGMENTED || CAUSAL, "segments are causal");
+  static_assert(!DROPOUT || !(RANGED || SEGMENTED), "dropout: DENSE only");
   constexpr int BN = 256;  // keys per block
   constexpr int BM = 64;   // q tile
   const int coff = SKV - SQ;  // bottom-right causal alignment
@@ -206,15 +219,15 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
         // registers: they would be carried across the loop as halves)
         const uint qw0[4] = {(uint)q0.x, (uint)q0.y, (uint)q0.z, (uint)q0.w};
         const uint qw1[4] = {(uint)q1.x, (uint)q1.y, (uint)q1.z, (uint)q1.w};
-        const uint dw0[4] = {(uint)d0.x, (uint)d0.y, (uint)d0.z, (uint)d0.w};
-        const uint dw1[4] = {(uint)d1.x, (uint)d1.y, (uint)d1.z, (uint)d1.w};
+        const uint rw0[4] = {(uint)d0.x, (uint)d0.y, (uint)d0.z, (uint)d0.w};
+        const uint rw1[4] = {(uint)d1.x, (uint)d1.y, (uint)d1.z, (uint)d1.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int m = j >> 1;
           const uint qp = (j & 1) ? (qw0[m] >> 16) | (qw1[m] & 0xffff0000u)
                                   : (qw0[m] & 0xffffu) | (qw1[m] << 16);
-          const uint dp = (j & 1) ? (dw0[m] >> 16) | (dw1[m] & 0xffff0000u)
-                                  : (dw0[m] & 0xffffu) | (dw1[m] << 16);
+          const uint dp = (j & 1) ? (rw0[m] >> 16) | (rw1[m] & 0xffff0000u)
+                                  : (rw0[m] & 0xffffu) | (rw1[m] << 16);
           const int r = sc + j;
           const uint byte = tr_swz((uint)(r * VP + sr) * 2, r);
           *(uint*)((char*)qt_lds + byte) = qp;
@@ -280,6 +293,21 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
           __builtin_amdgcn_sched_barrier(0);
           const f32x4_t lse = *(const f32x4_t*)&row_lds[nq * 16 + lq];
           const f32x4_t delta = *(const f32x4_t*)&row_lds[BM + nq * 16 + lq];
+          // DROPOUT: the lane's word of each 16-key strip (byte r = query
+          // lq + r); strip sb of wave wid is word (wid & 1) * 2 + sb of the
+          // block's call, a scalar choice
+          uint rw0 = 0u, rw1 = 0u;
+          float kscale = 1.f;
+          if constexpr (DROPOUT) {
+            const DropWords w4 = dropout_words(
+                drop_seed, drop_off, (uint)(b * HQ + hq),
+                (uint)(qbase + nq * 16 + lq) >> 2,
+                dropout_key_group(krow_w + l15));
+            const bool upper = (wid & 1) != 0;
+            rw0 = upper ? w4.w[2] : w4.w[0];
+            rw1 = upper ? w4.w[3] : w4.w[1];
+            kscale = dropout_keep_scale(drop_t);
+          }
           // interior fast path: every (q, key) of this 16-query x 32-key
           // patch in bounds and alive — no compare/selects
           bool full_patch =
@@ -302,9 +330,18 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const float p = __expf(st[sb][r] - lse[r]);
-                const float ds = p * (dpt[sb][r] - delta[r]) * scale;
-                p4[r] = (__bf16)p;
-                ds4[r] = (__bf16)ds;
+                if constexpr (DROPOUT) {
+                  // M * keep_scale
+                  const float mk =
+                      dropout_keep_byte(sb ? rw1 : rw0, r, drop_t) ? kscale : 0.f;
+                  const float ds = p * (dpt[sb][r] * mk - delta[r]) * scale;
+                  p4[r] = (__bf16)(p * mk);
+                  ds4[r] = (__bf16)ds;
+                } else {
+                  const float ds = p * (dpt[sb][r] - delta[r]) * scale;
+                  p4[r] = (__bf16)p;
+                  ds4[r] = (__bf16)ds;
+                }
               }
               const int at = (sb * 16 + l15) * VP + nq * 16 + lq;
               *(bf16x4_t*)&pw[at] = p4;
@@ -333,9 +370,18 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
                 if (CAUSAL && window > 0) dead |= (dl >= kd + window - r);
                 if constexpr (SEGMENTED) dead |= (l15 < qs[r] - k0);
                 const float p = dead ? 0.f : __expf(st[sb][r] - lse[r]);
-                const float ds = p * (dpt[sb][r] - delta[r]) * scale;
-                p4[r] = (__bf16)p;
-                ds4[r] = (__bf16)ds;
+                if constexpr (DROPOUT) {
+                  // M * keep_scale
+                  const float mk =
+                      dropout_keep_byte(sb ? rw1 : rw0, r, drop_t) ? kscale : 0.f;
+                  const float ds = p * (dpt[sb][r] * mk - delta[r]) * scale;
+                  p4[r] = (__bf16)(p * mk);
+                  ds4[r] = (__bf16)ds;
+                } else {
+                  const float ds = p * (dpt[sb][r] - delta[r]) * scale;
+                  p4[r] = (__bf16)p;
+                  ds4[r] = (__bf16)ds;
+                }
               }
               const int at = (sb * 16 + l15) * VP + nq * 16 + lq;
               *(bf16x4_t*)&pw[at] = p4;
@@ -398,15 +444,16 @@ __global__ __launch_bounds__(512) void flash_bwd_dkv_pipe_kernel(
 extern "C" void launch_flash_dkv_pipe(const FlashArgs& a, hipStream_t stream) {
   // one block per (kblock, b, hkv, g)
   const dim3 gkv((a.SKV + 255) / 256, a.B * a.HQ), blk(512);
-  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+  dispatch_flash_drop(a, [&](auto d, auto c, auto r, auto s, auto p) {
     flash_bwd_dkv_pipe_kernel<decltype(d)::value, decltype(c)::value,
-                              decltype(r)::value, decltype(s)::value>
+                              decltype(r)::value, decltype(s)::value,
+                              decltype(p)::value>
         <<<gkv, blk, 0, stream>>>(
             (const bf16*)a.dout, (const bf16*)a.q, (const bf16*)a.k,
             (const bf16*)a.v, (const float*)a.lse, (const float*)a.delta,
             (float*)a.dk, (float*)a.dv, a.SQ, a.SKV, a.B, a.HQ, a.HKV,
             a.scale, a.window, a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1],
             a.ks[2], a.vs[0], a.vs[1], a.vs[2], a.ds[0], a.ds[1], a.ds[2],
-            a.bound_a, a.bound_b);
+            a.bound_a, a.bound_b, a.drop_t, a.drop_seed, a.drop_offset);
   });
 }

@@ -5,6 +5,7 @@
 // LDS 108.5 KB -> 1 block/CU (8 waves) vs the single-buffered kernel's 2
 // blocks; measured +3.0% (bench shape) / +1.8% (TP=8 shape).
 #include "attn_common.h"
+#include "attn_dropout.h"
 #include "flash_dispatch.h"
 
 // NSB = 16-row sub-blocks per wave: 2 -> BM 256 (the TP<=4 shape), 1 ->
@@ -24,6 +25,14 @@
 // q_start is non-decreasing along a row, so a tile's bounds come from its
 // first / last row. Every query sees itself: no empty rows.
 
+// DROPOUT (DENSE mask only): O = ((P . M) V) * keep_scale / l with the keep
+// mask M of attn_dropout.h; l and LSE are those of the undropped softmax.
+// The dropped P goes to p_lds, so the ones-fragment MFMA over p_lds would
+// sum the wrong thing: these instantiations instead add the fp32 p into a
+// per-lane partial of l (alpha is uniform over the 16 lanes that share a
+// row, so the partials rescale like l itself) and reduce it across those
+// lanes once, in the epilogue. The other instantiations compile as before.
+
 // LDS home of the q_start values of a block's N query rows. The buffer
 // exists only in kernels that call this (the SEGMENTED ones), so the other
 // instantiations keep their LDS size.
@@ -34,7 +43,7 @@ __device__ __forceinline__ int* seg_bounds_lds() {
 }
 
 template <int D, bool CAUSAL, int NSB, bool RANGED = false,
-          bool SEGMENTED = false>
+          bool SEGMENTED = false, bool DROPOUT = false>
 __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     const bf16* __restrict__ Q, const bf16* __restrict__ K,
     const bf16* __restrict__ V, bf16* __restrict__ O,
@@ -45,9 +54,12 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
     long sKs, long sKb, long sKh,   // K strides
     long sVs, long sVb, long sVh,   // V strides
     const int* __restrict__ kv_lo = nullptr,   // [B] int32 (RANGED), or
-    const int* __restrict__ kv_hi = nullptr) { // [B, S] (SEGMENTED)
+    const int* __restrict__ kv_hi = nullptr,   // [B, S] (SEGMENTED)
+    int drop_t = 0,  // DROPOUT: threshold 1..255 and the random stream
+    unsigned long long drop_seed = 0, unsigned long long drop_off = 0) {
   static_assert(!(RANGED && SEGMENTED), "one mask mode at a time");
   static_assert(!SEGMENTED || CAUSAL, "segments are causal");
+  static_assert(!DROPOUT || !(RANGED || SEGMENTED), "dropout: DENSE only");
   constexpr int BM = NSB * 128, BN = 64;
   constexpr int KP = D + 8;
   constexpr int VP = BN + 8;
@@ -322,11 +334,27 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
 #pragma unroll
           for (int r = 0; r < 4; ++r) alpha_s[sb][r] = 1.0f;
         }
+        // DROPOUT: this lane's four keys of the tile (kbase + nk * 16 +
+        // (lane & 15)) x its four queries are the four words of one call;
+        // generated here, per sub-block, and dead after the loop below
+        DropWords dw;
+        if constexpr (DROPOUT) {
+          dw = dropout_words(
+              drop_seed, drop_off, (uint)bh,
+              (uint)(qrow_w + sb * 16 + (lane >> 4) * 4) >> 2,
+              dropout_key_group(kbase + (lane & 15)));
+#pragma unroll
+          for (int r = 0; r < 4; ++r) l_i[sb][r] *= alpha_s[sb][r];
+        }
 #pragma unroll
         for (int nk = 0; nk < 4; ++nk) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             float p = __expf(sv[nk][r] - m_i[sb][r]);
+            if constexpr (DROPOUT) {
+              l_i[sb][r] += p;  // lane partial of the undropped row sum
+              p = dropout_keep_byte(dw.w[nk], r, drop_t) ? p : 0.f;
+            }
             // a row with no alive key yet still has m_i = -1e30, so its
             // dead entries would get exp(0) = 1 (dense causal rows always
             // see themselves; rows below lo do not) — force them to 0.
@@ -352,15 +380,18 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
           for (int sb = 0; sb < NSB; ++sb) {
             bf16x8_t pa = load_frag_a(pw + sb * 16 * VP, VP, kk * 32, lane);
             oacc[sb][nj] = MFMA_16x16x32(pa, vb, oacc[sb][nj]);
-            if (nj == 0) racc[sb] = MFMA_16x16x32(pa, ones_frag, racc[sb]);
+            if constexpr (!DROPOUT)
+              if (nj == 0) racc[sb] = MFMA_16x16x32(pa, ones_frag, racc[sb]);
           }
         }
       }
+      if constexpr (!DROPOUT) {
 #pragma unroll
-      for (int sb = 0; sb < NSB; ++sb)
+        for (int sb = 0; sb < NSB; ++sb)
 #pragma unroll
-        for (int r = 0; r < 4; ++r)
-          l_i[sb][r] = l_i[sb][r] * alpha_s[sb][r] + racc[sb][r];
+          for (int r = 0; r < 4; ++r)
+            l_i[sb][r] = l_i[sb][r] * alpha_s[sb][r] + racc[sb][r];
+      }
     }
     // stage tile jb+1 into the OTHER buffer (its previous contents —
     // tile jb-1 — were last read before the barrier that ended jb-1, so
@@ -377,9 +408,20 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
 #pragma unroll
   for (int sb = 0; sb < NSB; ++sb) {
     float inv_l[4];
+    if constexpr (DROPOUT) {  // lane partials -> row sums
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int off = 1; off < 16; off <<= 1)
+          l_i[sb][r] += __shfl_xor(l_i[sb][r], off, 64);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       inv_l[r] = (l_i[sb][r] > 0.f) ? 1.f / l_i[sb][r] : 0.f;
+    if constexpr (DROPOUT) {  // keep_scale folds into the normalisation
+#pragma unroll
+      for (int r = 0; r < 4; ++r) inv_l[r] *= dropout_keep_scale(drop_t);
+    }
 #pragma unroll
     for (int nj = 0; nj < DN; ++nj) {
 #pragma unroll
@@ -404,16 +446,17 @@ __global__ __launch_bounds__(512) void flash_fwd_dbuf_kernel(
 extern "C" void launch_flash_fwd_dbuf(const FlashArgs& a, hipStream_t stream) {
   const int bm = flash_block_rows(a.SQ, a.B * a.HQ);
   const dim3 grid((a.SQ + bm - 1) / bm, a.B * a.HQ), blk(512);
-  dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+  dispatch_flash_drop(a, [&](auto d, auto c, auto r, auto s, auto p) {
     constexpr int D = decltype(d)::value;
     constexpr bool C = decltype(c)::value, R = decltype(r)::value,
-                   S = decltype(s)::value;
-    auto kern = bm == 128 ? flash_fwd_dbuf_kernel<D, C, 1, R, S>
-                          : flash_fwd_dbuf_kernel<D, C, 2, R, S>;
+                   S = decltype(s)::value, P = decltype(p)::value;
+    auto kern = bm == 128 ? flash_fwd_dbuf_kernel<D, C, 1, R, S, P>
+                          : flash_fwd_dbuf_kernel<D, C, 2, R, S, P>;
     kern<<<grid, blk, 0, stream>>>(
         (const bf16*)a.q, (const bf16*)a.k, (const bf16*)a.v, (bf16*)a.o,
         (float*)a.lse, a.SQ, a.SKV, a.B, a.HQ, a.HKV, a.scale, a.window,
         a.qs[0], a.qs[1], a.qs[2], a.ks[0], a.ks[1], a.ks[2], a.vs[0],
-        a.vs[1], a.vs[2], a.bound_a, a.bound_b);
+        a.vs[1], a.vs[2], a.bound_a, a.bound_b, a.drop_t, a.drop_seed,
+        a.drop_offset);
   });
 }

@@ -1,4 +1,4 @@
-// Runtime (D, causal, mask) -> compile-time constants for the flash-attention
+// Runtime (D, causal, mask, dropout) -> compile-time constants for the flash-attention
 // launchers (.hip files only). Each helper calls a generic lambda with
 // std::integral_constant arguments; the lambda reads them back with
 // decltype(x)::value and names its kernel once. The combinations enumerated
@@ -45,5 +45,21 @@ void dispatch_flash(const FlashArgs& a, F&& f) {
         f(d, c, std::true_type{}, std::false_type{});
       else
         f(d, c, std::false_type{}, std::false_type{});
+    });
+}
+
+// dispatch_flash plus a fifth argument bool_constant<DROPOUT>, for the three
+// kernels with a DROPOUT flag: a.drop_t > 0 adds D x {causal, non-causal}
+// with DROPOUT set, DENSE only (the bindings never set drop_t with another
+// mask mode, and the kernels static_assert against it)
+template <class F>
+void dispatch_flash_drop(const FlashArgs& a, F&& f) {
+  if (a.drop_t > 0)
+    dispatch_dense(a, [&](auto d, auto c) {
+      f(d, c, std::false_type{}, std::false_type{}, std::true_type{});
+    });
+  else
+    dispatch_flash(a, [&](auto d, auto c, auto r, auto s) {
+      f(d, c, r, s, std::false_type{});
     });
 }

@@ -33,6 +33,12 @@ struct FlashArgs {
   long qs[3], ks[3], vs[3], ds[3];  // q, k, v, dout strides
   Mask mask;
   const int *bound_a, *bound_b;
+  // Attention dropout (attn_dropout.h), DENSE only: drop_t = round(256 * p)
+  // in 1..255 selects the DROPOUT instantiations of the double-buffered
+  // forward, the dQ kernel and the pipelined dK/dV kernel; 0 = no dropout
+  // (every other call). (drop_seed, drop_offset) name the random stream.
+  int drop_t;
+  unsigned long long drop_seed, drop_offset;
 };
 
 // Query rows per block of the forward and dQ grids: 128 when the 256-row grid
@@ -47,16 +53,23 @@ static_assert(flash_block_rows(300, 255) == 128, "510 blocks: 128-row tiles");
 extern "C" {
 // flash_attn_fwd.hip: single-buffered forward (A/B arm), DENSE only
 void launch_flash_fwd(const FlashArgs& a, hipStream_t stream);
-// flash_attn_fwd_dbuf.hip: double-buffered forward (default), every mask
+// flash_attn_fwd_dbuf.hip: double-buffered forward (default), every mask,
+// dropout
 void launch_flash_fwd_dbuf(const FlashArgs& a, hipStream_t stream);
 // flash_attn_bwd.hip: dK/dV, then dQ. pipe = true: dK/dV by the pipelined
-// kernel (default); false: by flash_bwd_dkv_kernel (A/B arm, bit-equal)
+// kernel (default); false: by flash_bwd_dkv_kernel (A/B arm, bit-equal).
+// A dropout call (drop_t > 0) always takes the pipelined kernel.
 void launch_flash_bwd(const FlashArgs& a, bool pipe, hipStream_t stream);
 // flash_attn_bwd_dkv_pipe.hip: dK/dV only; called by launch_flash_bwd
 void launch_flash_dkv_pipe(const FlashArgs& a, hipStream_t stream);
 // v3 kernels: DENSE only, SQ == SKV
 void launch_flash_fwd_v3(const FlashArgs& a, hipStream_t stream);
 void launch_flash_bwd_v3(const FlashArgs& a, hipStream_t stream);
+// attn_dropout.hip: keep mask [B, HQ, SQ, SKV] uint8 (1 = keep), the mask the
+// DROPOUT kernels regenerate; test and debug support
+void launch_attn_dropout_mask(void* mask, int B, int HQ, int SQ, int SKV,
+                              int drop_t, unsigned long long seed,
+                              unsigned long long offset, hipStream_t stream);
 void launch_attn_delta(const void* dout, const void* o, void* delta, int SQ,
                        int B, int HQ, int D, const long* dstr,
                        const long* ostr, hipStream_t stream);

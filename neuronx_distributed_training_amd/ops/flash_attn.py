@@ -25,6 +25,11 @@ Every query sees itself, so there are no empty rows. The kernels take the
 two derived arrays of :func:`segment_bounds`, not the ids. Segmented calls
 need ``S_q == S_kv`` and ``causal=True``, exclude ``kv_range`` and always
 run the v2 kernels.
+
+Attention dropout: ``dropout_p`` drops probabilities inside the kernels with
+a counter-based keep mask that forward and backward regenerate from
+``(seed, offset)`` (``dropout_rng``, or the device's default generator).
+Dense masks only; always the v2 kernels. See :func:`flash_attn_func`.
 """
 
 from __future__ import annotations
@@ -151,6 +156,74 @@ def segment_bounds(segment_ids):
             k_end.to(torch.int32).contiguous())
 
 
+_U64 = (1 << 64) - 1
+
+
+def dropout_threshold(p: float) -> int:
+    """8-bit drop threshold ``t = round(256 * p)``: an element is dropped
+    iff its random byte is below t. 0 means no dropout; ``p`` outside
+    ``[0, 1)``, or so close to 1 that t would be 256, raises ValueError."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"dropout_p must be in [0, 1), got {p}")
+    t = int(math.floor(256.0 * p + 0.5))
+    if t > 255:
+        raise ValueError(
+            f"dropout_p {p} rounds to 256/256: the threshold has 8 bits"
+        )
+    return t
+
+
+def dropout_keep_scale(p: float) -> float:
+    """Factor on kept probabilities, ``256 / (256 - t)``: the inverse of the
+    quantised keep probability, so the expectation is exact."""
+    return 256.0 / (256 - dropout_threshold(p))
+
+
+def draw_dropout_rng(device):
+    """(seed, offset) from the default generator of `device`, which is
+    advanced: ``torch.manual_seed``, ``torch.cuda.set_rng_state`` and
+    ``RNGStatesTracker.fork()`` govern the pair and successive draws differ.
+    No device sync."""
+    if device.type == "cuda":
+        idx = device.index
+        if idx is None:
+            idx = torch.cuda.current_device()
+        gen = torch.cuda.default_generators[idx]
+        seed, offset = gen.initial_seed(), gen.get_offset()
+        gen.set_offset(offset + 4)  # the generator wants multiples of 4
+        return int(seed) & _U64, int(offset) & _U64
+    # the CPU generator has no offset: draw one from its stream
+    gen = torch.default_generator
+    offset = int(torch.randint(0, 1 << 62, (1,), generator=gen))
+    return int(gen.initial_seed()) & _U64, offset
+
+
+def dropout_keep_mask(b, hq, sq, skv, p, rng, device):
+    """Bool [b, hq, sq, skv], True = keep: exactly the mask a
+    ``flash_attn_func`` call with ``dropout_p=p, dropout_rng=rng`` applies to
+    its probabilities on `device`. On GPU it is written by the kernel-side
+    definition (``flash_attn_dropout_mask``), a pure function of
+    ``(seed, offset, b, hq, i, j, t)``; on CPU it comes from a
+    ``torch.Generator`` seeded from ``(seed, offset)``, and is a function of
+    the four sizes as well."""
+    t = dropout_threshold(p)
+    seed, offset = int(rng[0]) & _U64, int(rng[1]) & _U64
+    device = torch.device(device)
+    if device.type == "cuda":
+        from . import require_extension
+
+        with torch.cuda.device(device):
+            m = require_extension().flash_attn_dropout_mask(
+                b, hq, sq, skv, float(p), seed, offset
+            )
+        return m != 0
+    gen = torch.Generator()
+    gen.manual_seed((seed * 0x9E3779B97F4A7C15 + offset) & ((1 << 63) - 1))
+    byte = torch.randint(0, 256, (b, hq, sq, skv), generator=gen)
+    return byte >= t
+
+
 def _make_mask(sq, sk, causal, window, device, kv_lo=None, kv_hi=None,
                q_start=None):
     """True = dead. [sq, sk], or [b, 1, sq, sk] with a key range or
@@ -194,8 +267,16 @@ def _ranged_softmax(s, mask):
     return p, lse.squeeze(-1)
 
 
+def _cpu_drop_factor(q, k, drop):
+    """keep mask * keep_scale of drop = (p, seed, offset), fp32."""
+    p, seed, offset = drop
+    keep = dropout_keep_mask(q.size(0), q.size(1), q.size(2), k.size(2), p,
+                             (seed, offset), q.device)
+    return keep.float() * dropout_keep_scale(p)
+
+
 def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None,
-                 q_start=None):
+                 q_start=None, drop=None):
     hq, hkv = q.size(1), k.size(1)
     if hq != hkv:
         k = k.repeat_interleave(hq // hkv, dim=1)
@@ -210,6 +291,8 @@ def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None,
         s = s.masked_fill(mask, float("-inf"))
         lse = torch.logsumexp(s, dim=-1)
         p = torch.softmax(s, dim=-1)
+    if drop is not None:      # LSE stays that of the undropped softmax
+        p = p * _cpu_drop_factor(q, k, drop)
     o = torch.matmul(p, vf)
     return o.to(q.dtype), lse
 
@@ -217,11 +300,18 @@ def _cpu_ref_fwd(q, k, v, causal, scale, window=0, kv_lo=None, kv_hi=None,
 class _FlashAttnFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, causal: bool, scale: float, window: int = 0,
-                kv_lo=None, kv_hi=None, q_start=None, k_end=None):
+                kv_lo=None, kv_hi=None, q_start=None, k_end=None, drop=None):
+        # drop: None, or (p, seed, offset) with t > 0, as Python numbers; the
+        # backward regenerates the mask from them (no mask tensor is saved)
         kern = kernels_for(q)
         ranged = kv_lo is not None
         segmented = q_start is not None
-        if kern is not None and segmented:
+        if kern is not None and drop is not None:
+            # dropout calls always use the v2 kernels
+            o, lse = kern.flash_attn_fwd_drop(
+                q, k, v, causal, scale, window, *drop
+            )
+        elif kern is not None and segmented:
             # segmented calls always use the v2 kernels too
             o, lse = kern.flash_attn_fwd_seg(
                 q, k, v, q_start, k_end, scale, window
@@ -238,7 +328,7 @@ class _FlashAttnFn(torch.autograd.Function):
             )
         else:
             o, lse = _cpu_ref_fwd(q, k, v, causal, scale, window,
-                                  kv_lo, kv_hi, q_start)
+                                  kv_lo, kv_hi, q_start, drop)
         if segmented:
             ctx.save_for_backward(q, k, v, o, lse, q_start, k_end)
         elif ranged:
@@ -250,12 +340,13 @@ class _FlashAttnFn(torch.autograd.Function):
         ctx.causal = causal
         ctx.scale = scale
         ctx.window = window
+        ctx.drop = drop
         return o
 
     @staticmethod
     def backward(ctx, do):
         kv_lo = kv_hi = q_start = k_end = None
-        none7 = (None,) * 7
+        none7 = (None,) * 8
         if ctx.segmented:
             q, k, v, o, lse, q_start, k_end = ctx.saved_tensors
         elif ctx.ranged:
@@ -263,6 +354,13 @@ class _FlashAttnFn(torch.autograd.Function):
         else:
             q, k, v, o, lse = ctx.saved_tensors
         kern = kernels_for(q)
+        if kern is not None and ctx.drop is not None:
+            # always the pipelined dK/dV kernel, whatever NXDT_ATTN_DKV says
+            dq, dk, dv = kern.flash_attn_bwd_drop(
+                do, q, k, v, o, lse, ctx.causal, ctx.scale, ctx.window,
+                *ctx.drop
+            )
+            return (dq, dk, dv) + none7
         if kern is not None and ctx.segmented:
             dq, dk, dv = v2_bwd_fn(kern, "_seg")(
                 do, q, k, v, o, lse, q_start, k_end, ctx.scale, ctx.window
@@ -293,8 +391,14 @@ class _FlashAttnFn(torch.autograd.Function):
         else:
             s = s.masked_fill(mask, float("-inf"))
             p = torch.softmax(s, dim=-1)
-        dv = torch.matmul(p.transpose(-1, -2), dof)
-        dp = torch.matmul(dof, vx.transpose(-1, -2))
+        if ctx.drop is None:
+            dv = torch.matmul(p.transpose(-1, -2), dof)
+            dp = torch.matmul(dof, vx.transpose(-1, -2))
+        else:
+            # dV = (P . M ks)^T dO ; dS = P . (M ks . dP - delta) * scale
+            mk = _cpu_drop_factor(q, k, ctx.drop)
+            dv = torch.matmul((p * mk).transpose(-1, -2), dof)
+            dp = torch.matmul(dof, vx.transpose(-1, -2)) * mk
         delta = (dof * o.float()).sum(-1, keepdim=True)
         ds = p * (dp - delta) * ctx.scale
         dq = torch.matmul(ds, kx)
@@ -315,6 +419,8 @@ def flash_attn_func(
     kv_range=None,
     segment_ids=None,
     seg_bounds=None,
+    dropout_p: float = 0.0,
+    dropout_rng=None,
 ) -> torch.Tensor:
     """window: sliding-window size (attend to the last `window` keys);
     None/0 disables (Mixtral sliding_window parity).
@@ -328,9 +434,47 @@ def flash_attn_func(
     ``j <= i`` and j is inside the window; a pad tail is its own trailing
     segment. Needs ``causal=True`` and ``S_q == S_kv``; excludes
     ``kv_range``. ``seg_bounds`` passes the precomputed result of
-    :func:`segment_bounds` instead (a model computes it once per forward)."""
+    :func:`segment_bounds` instead (a model computes it once per forward).
+
+    dropout_p: dropout on the attention probabilities, inside the kernels:
+    ``O = ((P . M) V) * keep_scale`` with a keep mask M that the forward,
+    the dQ and the dK/dV kernel each regenerate from a counter-based
+    generator (no mask tensor exists or is saved). Probabilities have 8
+    bits: an element is dropped with probability ``t / 256``,
+    ``t = round(256 * dropout_p)``, and kept ones are scaled by
+    ``256 / (256 - t)`` (:func:`dropout_keep_scale`). 0.0, or any value
+    that rounds to ``t == 0``, takes exactly the code path of a call
+    without the argument. The caller decides when dropout applies (a model
+    passes 0.0 in eval mode). Dense masks only: ``kv_range``,
+    ``segment_ids`` and ``seg_bounds`` raise ValueError with
+    ``dropout_p > 0``, as does ``dropout_p`` outside ``[0, 1)``. Dropout
+    calls always run the v2 kernels, with the pipelined dK/dV kernel.
+
+    dropout_rng: ``(seed, offset)``, two ints that fix the random stream;
+    :func:`dropout_keep_mask` returns the mask such a call uses. None draws
+    the pair from the default generator of ``q``'s device and advances it
+    (no device sync), so ``torch.manual_seed``, ``torch.cuda.set_rng_state``
+    and ``RNGStatesTracker.fork()`` govern it and successive calls differ.
+    The pair is read on the host when the call is made, so hipGraph capture
+    of a call with ``dropout_p > 0`` is not supported: every replay would
+    reuse the captured pair."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.size(-1))
+    if dropout_p != 0.0 and dropout_threshold(dropout_p) > 0:
+        if kv_range is not None:
+            raise ValueError("dropout_p > 0 does not support kv_range")
+        if segment_ids is not None or seg_bounds is not None:
+            raise ValueError(
+                "dropout_p > 0 does not support segment_ids / seg_bounds"
+            )
+        if dropout_rng is None:
+            dropout_rng = draw_dropout_rng(q.device)
+        drop = (float(dropout_p), int(dropout_rng[0]) & _U64,
+                int(dropout_rng[1]) & _U64)
+        return _FlashAttnFn.apply(
+            q, k, v, causal, scale, int(window or 0), None, None, None, None,
+            drop,
+        )
     if segment_ids is not None or seg_bounds is not None:
         if segment_ids is not None and seg_bounds is not None:
             raise ValueError("give segment_ids or seg_bounds, not both")

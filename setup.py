@@ -31,6 +31,7 @@ sources = [
         "flash_attn_bwd_v3.hip",
         "flash_attn_bwd.hip",
         "flash_attn_bwd_dkv_pipe.hip",
+        "attn_dropout.hip",
         "cross_entropy.hip",
         "moe_gemm.hip",
         "probe.hip",

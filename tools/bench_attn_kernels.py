@@ -3,10 +3,13 @@ swapped-operand, register softmax) at the headline bench shape.
 
 Run on a GPU box:
     python tools/bench_attn_kernels.py [--iters 20] [--seq 8192] [--batch 2]
+                                       [--dropout P]
 
 Prints per-kernel ms and effective TFLOP/s plus max-abs numeric drift
 between the two generations, so the dispatch default in ops/flash_attn.py
-can be flipped on evidence (VERDICT round-1 item #3).
+can be flipped on evidence (VERDICT round-1 item #3). --dropout P adds a
+third arm: the v2 kernels with attention dropout P (flash_attn_fwd_drop /
+flash_attn_bwd_drop), timed in the same session as the p = 0 arms.
 """
 
 import argparse
@@ -45,6 +48,8 @@ def main():
     ap.add_argument("--hq", type=int, default=32)
     ap.add_argument("--hkv", type=int, default=8)
     ap.add_argument("--d", type=int, default=128)
+    ap.add_argument("--dropout", type=float, default=0.0,
+                    help="also time the v2 kernels with this dropout_p")
     args = ap.parse_args()
 
     from neuronx_distributed_training_amd.ops import require_extension
@@ -61,11 +66,19 @@ def main():
     fF = flops_attn_fwd(b, hq, s, d)
     fB = fF * 2.5  # dq: 2 matmuls, dkv: 3 matmuls vs fwd's 2
 
-    results = {}
-    for name, fwd, bwd in (
+    arms = [
         ("v2", k.flash_attn_fwd, k.flash_attn_bwd),
         ("v3", k.flash_attn_fwd_v3, k.flash_attn_bwd_v3),
-    ):
+    ]
+    if args.dropout > 0:
+        pd, rng = args.dropout, (1234, 0)
+        arms.append((
+            f"v2 dropout {pd}",
+            lambda *a: k.flash_attn_fwd_drop(*a, pd, *rng),
+            lambda *a: k.flash_attn_bwd_drop(*a, pd, *rng),
+        ))
+    results = {}
+    for name, fwd, bwd in arms:
         o, lse = fwd(q, kk, v, True, scale, 0)
         do = torch.randn_like(o)
         tf = time_fn(lambda: fwd(q, kk, v, True, scale, 0), args.iters)
