@@ -3,9 +3,12 @@
 Every op has two paths:
 - the in-tree HIP extension (``_C``), built by ``setup.py build_ext
   --inplace`` / ``__graft_entry__.build()`` for gfx950 — the ONLY path used
-  on a GPU device; if the extension is missing while a tensor is on GPU the
-  op raises instead of silently falling back;
-- a plain PyTorch fp32 reference path used on CPU (unit tests, gloo runs).
+  for the dtypes the kernels are written for (bf16 activations) on a GPU
+  device; if the extension is missing while such a tensor is on GPU the op
+  raises instead of silently falling back;
+- a plain PyTorch fp32 reference path used on CPU (unit tests, gloo runs)
+  and, for RMSNorm / SwiGLU / RoPE, for GPU tensors that are not bf16 and
+  so have no kernel (``bf16_kernels_for``).
 
 Kernel inventory (replacing the reference's NKI/apex device stack, SURVEY.md
 §2.3): rmsnorm fwd/bwd, rope fwd/bwd, swiglu fwd/bwd, flash attention
@@ -77,6 +80,16 @@ def kernels_for(t: torch.Tensor):
     return None
 
 
+def bf16_kernels_for(t: torch.Tensor):
+    """The extension for a bf16 GPU tensor: the RMSNorm, SwiGLU and RoPE
+    kernels read bf16 and nothing else. None for CPU tensors and for GPU
+    tensors of any other dtype (fp32 / fp16 / fp64 modules), which have no
+    kernel and take the plain torch formulas on their own device."""
+    if t.is_cuda and t.dtype == torch.bfloat16:
+        return require_extension()
+    return None
+
+
 from .rmsnorm import rmsnorm  # noqa: E402
 from .rope import apply_rotary_pos_emb  # noqa: E402
 from .swiglu import swiglu  # noqa: E402
@@ -92,6 +105,7 @@ __all__ = [
     "have_extension",
     "require_extension",
     "kernels_for",
+    "bf16_kernels_for",
     "rmsnorm",
     "apply_rotary_pos_emb",
     "swiglu",

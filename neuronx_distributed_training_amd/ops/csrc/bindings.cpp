@@ -20,44 +20,84 @@ hipStream_t cur_stream() {
   TORCH_CHECK((t).is_cuda(), #t " must be on GPU");             \
   TORCH_CHECK((t).is_contiguous(), #t " must be contiguous")
 
+// The elementwise kernels index their arguments as dense arrays of one fixed
+// type with no strides, so every tensor they read is checked here, before
+// the launch: a dense tensor of `type` on the GPU of `ref` (t itself when it
+// is the first argument) ...
+static void check_dense(const torch::Tensor& t, const torch::Tensor& ref,
+                        c10::ScalarType type, const char* op,
+                        const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), op, ": ", name,
+              " must be on the GPU of the first argument");
+  TORCH_CHECK(t.scalar_type() == type, op, ": ", name, " must be ",
+              c10::toString(type));
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name, " must be contiguous");
+}
+
+// ... and, for a per-row or per-column vector, of exactly n elements.
+static void check_vec(const torch::Tensor& t, const torch::Tensor& ref,
+                      c10::ScalarType type, long n, const char* op,
+                      const char* name) {
+  check_dense(t, ref, type, op, name);
+  TORCH_CHECK(t.numel() == n, op, ": ", name, " must have ", n,
+              " elements, got ", t.numel());
+}
+
 std::vector<torch::Tensor> rmsnorm_fwd(torch::Tensor x, torch::Tensor w,
                                        double eps) {
   CHECK_IN(x);
   CHECK_IN(w);
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "rmsnorm: bf16 only");
   TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "rmsnorm: w must be bf16");
+  TORCH_CHECK(x.dim() == 2, "rmsnorm: x must be [N, H]");
   auto N = x.size(0);
   auto H = x.size(1);
   TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  check_vec(w, x, torch::kBFloat16, H, "rmsnorm", "w");
   auto y = torch::empty_like(x);
   auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  if (N == 0 || H == 0) return {y, invrms};
   launch_rmsnorm_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
                      invrms.data_ptr(), N, (int)H, (float)eps, cur_stream());
   return {y, invrms};
 }
 
+// Returns {dx bf16 [N, H], dw fp32 [H]}: dw is the kernel's fp32 sum itself;
+// the caller casts it to the dtype of its weight.
 std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
                                        torch::Tensor w, torch::Tensor invrms) {
   CHECK_IN(dy);
   CHECK_IN(x);
   CHECK_IN(w);
   TORCH_CHECK(w.scalar_type() == torch::kBFloat16, "rmsnorm: w must be bf16");
+  check_dense(x, x, torch::kBFloat16, "rmsnorm_bwd", "x");
+  TORCH_CHECK(x.dim() == 2, "rmsnorm_bwd: x must be [N, H]");
   auto N = x.size(0);
   auto H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  check_dense(dy, x, torch::kBFloat16, "rmsnorm_bwd", "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "rmsnorm_bwd: dy must have x's shape");
+  check_vec(w, x, torch::kBFloat16, H, "rmsnorm_bwd", "w");
+  check_vec(invrms, x, torch::kFloat32, N, "rmsnorm_bwd", "invrms");
   auto dx = torch::empty_like(x);
   auto dw32 = torch::zeros({H}, x.options().dtype(torch::kFloat32));
+  if (N == 0 || H == 0) return {dx, dw32};
   launch_rmsnorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
                      invrms.data_ptr(), dx.data_ptr(), dw32.data_ptr(), N,
                      (int)H, cur_stream());
-  return {dx, dw32.to(w.scalar_type())};
+  return {dx, dw32};
 }
 
 torch::Tensor swiglu_fwd(torch::Tensor gu) {
   CHECK_IN(gu);
+  check_dense(gu, gu, torch::kBFloat16, "swiglu_fwd", "gate_up");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) % 2 == 0,
+              "swiglu_fwd: gate_up must be [N, 2 * I]");
   auto N = gu.size(0);
   auto I = gu.size(1) / 2;
   TORCH_CHECK(I % 8 == 0, "intermediate must be divisible by 8");
   auto y = torch::empty({N, I}, gu.options());
+  if (N == 0 || I == 0) return y;
   launch_swiglu_fwd(gu.data_ptr(), y.data_ptr(), N, (int)I, cur_stream());
   return y;
 }
@@ -65,9 +105,17 @@ torch::Tensor swiglu_fwd(torch::Tensor gu) {
 torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu) {
   CHECK_IN(dy);
   CHECK_IN(gu);
+  check_dense(gu, gu, torch::kBFloat16, "swiglu_bwd", "gate_up");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) % 2 == 0,
+              "swiglu_bwd: gate_up must be [N, 2 * I]");
   auto N = gu.size(0);
   auto I = gu.size(1) / 2;
+  TORCH_CHECK(I % 8 == 0, "intermediate must be divisible by 8");
+  check_dense(dy, gu, torch::kBFloat16, "swiglu_bwd", "dy");
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) == N && dy.size(1) == I,
+              "swiglu_bwd: dy must be [N, I]");
   auto dgu = torch::empty_like(gu);
+  if (N == 0 || I == 0) return dgu;
   launch_swiglu_bwd(dy.data_ptr(), gu.data_ptr(), dgu.data_ptr(), N, (int)I,
                     cur_stream());
   return dgu;
@@ -82,13 +130,35 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
   // pos_offset2 + i instead of pos_offset + s/2 + i.
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.stride(3) == 1,
               "rope: x must be [b, h, s, d] on GPU with d contiguous");
-  auto cos_c = cost.contiguous();
-  auto sin_c = sint.contiguous();
-  TORCH_CHECK(cos_c.scalar_type() == torch::kFloat32, "rope table must be f32");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "rope: x must be bf16");
   int B = (int)x.size(0), H = (int)x.size(1), S = (int)x.size(2),
       D = (int)x.size(3);
+  // the kernel pairs column d with d + D / 2
+  TORCH_CHECK(D % 2 == 0, "rope: head_dim must be even, got ", D);
   TORCH_CHECK(pos_offset2 < 0 || S % 2 == 0, "zigzag rope needs even s");
+  // Both tables are read as dense fp32 [rows, D] at rows pos_offset + i; in
+  // the zigzag layout the first half reads pos_offset + [0, S / 2) and the
+  // second pos_offset2 + [0, S / 2).
+  const long first = pos_offset2 < 0 ? S : S / 2;
+  long need = pos_offset + first;
+  if (pos_offset2 >= 0 && pos_offset2 + S / 2 > need)
+    need = pos_offset2 + S / 2;
+  TORCH_CHECK(pos_offset >= 0, "rope: pos_offset must be >= 0");
+  for (const torch::Tensor* t : {&cost, &sint}) {
+    const char* name = t == &cost ? "cos" : "sin";
+    TORCH_CHECK(t->is_cuda() && t->device() == x.device(), "rope: ", name,
+                " table must be on x's GPU");
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, "rope: ", name,
+                " table must be f32");
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == D, "rope: ", name,
+                " table must be [rows, head_dim]");
+    TORCH_CHECK(S == 0 || t->size(0) >= need, "rope: ", name, " table has ",
+                t->size(0), " rows, positions reach ", need);
+  }
+  auto cos_c = cost.contiguous();
+  auto sin_c = sint.contiguous();
   auto y_mem = torch::empty({S, B, H, D}, x.options());
+  if (y_mem.numel() == 0) return y_mem.permute({1, 2, 0, 3});
   long xstr[3] = {x.stride(2), x.stride(0), x.stride(1)};  // s, b, h
   launch_rope_fwd(x.data_ptr(), cos_c.data_ptr(), sin_c.data_ptr(),
                   y_mem.data_ptr(), S, B, H, D, xstr, (int)pos_offset,
@@ -632,12 +702,17 @@ std::vector<torch::Tensor> ce_fwd(torch::Tensor logits, torch::Tensor targets,
   CHECK_IN(logits);
   TORCH_CHECK(logits.scalar_type() == torch::kBFloat16, "ce: bf16 logits");
   TORCH_CHECK(targets.scalar_type() == torch::kLong, "ce: int64 targets");
+  TORCH_CHECK(logits.dim() == 2, "ce: logits must be [N, V]");
   long N = logits.size(0);
   int V = (int)logits.size(1);
+  TORCH_CHECK(targets.is_cuda() && targets.device() == logits.device(),
+              "ce: targets must be on the GPU of logits");
+  TORCH_CHECK(targets.numel() == N, "ce: targets must have N elements");
   auto opt = logits.options().dtype(torch::kFloat32);
   auto row_max = torch::empty({N}, opt);
   auto row_sumexp = torch::empty({N}, opt);
   auto tgt = torch::empty({N}, opt);
+  if (N == 0) return {row_max, row_sumexp, tgt};
   launch_ce_fwd(logits.data_ptr(), targets.contiguous().data_ptr(),
                 row_max.data_ptr(), row_sumexp.data_ptr(), tgt.data_ptr(), N,
                 V, vocab_start, cur_stream());
@@ -648,9 +723,29 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor targets,
                      torch::Tensor gmax, torch::Tensor gsum,
                      torch::Tensor gout, long vocab_start) {
   CHECK_IN(logits);
+  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16, "ce: bf16 logits");
+  TORCH_CHECK(logits.dim() == 2, "ce: logits must be [N, V]");
   long N = logits.size(0);
   int V = (int)logits.size(1);
+  // per-row vectors the kernel indexes by row; a strided one is copied below
+  const struct {
+    const torch::Tensor& t;
+    c10::ScalarType type;
+    const char* name;
+  } rows[] = {{targets, torch::kLong, "targets"},
+              {gmax, torch::kFloat32, "gmax"},
+              {gsum, torch::kFloat32, "gsum"},
+              {gout, torch::kFloat32, "gout"}};
+  for (const auto& r : rows) {
+    TORCH_CHECK(r.t.is_cuda() && r.t.device() == logits.device(), "ce_bwd: ",
+                r.name, " must be on the GPU of logits");
+    TORCH_CHECK(r.t.scalar_type() == r.type, "ce_bwd: ", r.name, " must be ",
+                c10::toString(r.type));
+    TORCH_CHECK(r.t.numel() == N, "ce_bwd: ", r.name,
+                " must have N elements");
+  }
   auto dl = torch::empty_like(logits);
+  if (dl.numel() == 0) return dl;
   launch_ce_bwd(logits.data_ptr(), targets.contiguous().data_ptr(),
                 gmax.contiguous().data_ptr(), gsum.contiguous().data_ptr(),
                 gout.contiguous().data_ptr(), dl.data_ptr(), N, V,

@@ -2,6 +2,9 @@
 // Wavefront = 64 lanes; block sizes are multiples of 64.
 #pragma once
 
+#include <stdexcept>
+#include <string>
+
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
@@ -55,11 +58,16 @@ DEVINL float block_reduce_sum(float v, float* lds /* >= NT/64 floats */) {
   return r;
 }
 
+// After a kernel launch in a host launcher: a launch the runtime refused
+// (grid, block or LDS request out of range) throws instead of leaving the
+// caller with outputs nobody wrote. pybind11 turns it into a RuntimeError.
 #define HIP_CHECK_LAST()                                            \
   do {                                                              \
     hipError_t e = hipGetLastError();                               \
     if (e != hipSuccess) {                                          \
-      printf("HIP error %s at %s:%d\n", hipGetErrorString(e),       \
-             __FILE__, __LINE__);                                   \
+      throw std::runtime_error(std::string("HIP launch failed: ") + \
+                               hipGetErrorString(e) + " at " +      \
+                               __FILE__ + ":" +                     \
+                               std::to_string(__LINE__));           \
     }                                                               \
   } while (0)

@@ -116,15 +116,19 @@ extern "C" {
 void launch_ce_fwd(const void* logits, const void* targets, void* row_max,
                    void* row_sumexp, void* tgt_logit, long N, int V,
                    long vocab_start, hipStream_t stream) {
+  if (N <= 0) return;  // a grid of zero blocks is an invalid launch
   ce_fwd_kernel<256><<<dim3((unsigned)N), dim3(256), 0, stream>>>(
       (const bf16*)logits, (const long*)targets, (float*)row_max,
       (float*)row_sumexp, (float*)tgt_logit, V, vocab_start);
+  HIP_CHECK_LAST();
 }
 void launch_ce_bwd(const void* logits, const void* targets, const void* gmax,
                    const void* gsum, const void* gout, void* dlogits, long N,
                    int V, long vocab_start, hipStream_t stream) {
+  if (N <= 0) return;
   ce_bwd_kernel<256><<<dim3((unsigned)N), dim3(256), 0, stream>>>(
       (const bf16*)logits, (const long*)targets, (const float*)gmax,
       (const float*)gsum, (const float*)gout, (bf16*)dlogits, V, vocab_start);
+  HIP_CHECK_LAST();
 }
 }

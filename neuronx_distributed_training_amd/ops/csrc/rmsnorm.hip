@@ -122,18 +122,22 @@ extern "C" {
 void launch_rmsnorm_fwd(const void* x, const void* w, void* y, void* invrms,
                         long N, int H, float eps, hipStream_t stream) {
   constexpr int NT = 256;
+  if (N <= 0) return;  // a grid of zero blocks is an invalid launch
   rmsnorm_fwd_kernel<NT><<<dim3((unsigned)N), dim3(NT), 0, stream>>>(
       (const bf16*)x, (const bf16*)w, (bf16*)y, (float*)invrms, H, eps);
+  HIP_CHECK_LAST();
 }
 
 void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                         const void* invrms, void* dx, void* dw, long N, int H,
                         hipStream_t stream) {
   constexpr int NT = 256;
+  if (N <= 0) return;
   int blocks = (int)min((long)1024, N);
   size_t shmem = (H + NT / 64) * sizeof(float);
   rmsnorm_bwd_kernel<NT><<<dim3(blocks), dim3(NT), shmem, stream>>>(
       (const bf16*)dy, (const bf16*)x, (const bf16*)w, (const float*)invrms,
       (bf16*)dx, (float*)dw, (int)N, H);
+  HIP_CHECK_LAST();
 }
 }

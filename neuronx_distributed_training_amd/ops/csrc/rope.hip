@@ -47,9 +47,11 @@ void launch_rope_fwd(const void* x, const void* cost, const void* sint,
                      int pos_offset, int pos_offset2, float sin_sign,
                      hipStream_t stream) {
   long total = (long)S * B * H * (D >> 1);
+  if (total <= 0) return;  // a grid of zero blocks is an invalid launch
   int blocks = (int)min((total + 255) / 256, (long)16384);
   rope_fwd_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(
       (const bf16*)x, (const float*)cost, (const float*)sint, (bf16*)y, S, B,
       H, D, xstr[0], xstr[1], xstr[2], pos_offset, pos_offset2, sin_sign);
+  HIP_CHECK_LAST();
 }
 }

@@ -76,15 +76,19 @@ extern "C" {
 void launch_swiglu_fwd(const void* gu, void* y, long N, int I,
                        hipStream_t stream) {
   long total = N * (long)(I >> 3);
+  if (total <= 0) return;  // a grid of zero blocks is an invalid launch
   int blocks = (int)min((total + 255) / 256, (long)8192);
   swiglu_fwd_kernel<<<dim3(blocks), dim3(256), 0, stream>>>((const bf16*)gu,
                                                             (bf16*)y, N, I);
+  HIP_CHECK_LAST();
 }
 void launch_swiglu_bwd(const void* dy, const void* gu, void* dgu, long N,
                        int I, hipStream_t stream) {
   long total = N * (long)(I >> 3);
+  if (total <= 0) return;
   int blocks = (int)min((total + 255) / 256, (long)8192);
   swiglu_bwd_kernel<<<dim3(blocks), dim3(256), 0, stream>>>(
       (const bf16*)dy, (const bf16*)gu, (bf16*)dgu, N, I);
+  HIP_CHECK_LAST();
 }
 }

@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import kernels_for
+from . import bf16_kernels_for
 
 
 def _kernel_weight(weight: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
@@ -25,7 +25,7 @@ def _kernel_weight(weight: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
 class _RMSNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x: torch.Tensor, weight: torch.Tensor, eps: float):
-        k = kernels_for(x)
+        k = bf16_kernels_for(x)
         shp = x.shape
         x2 = x.reshape(-1, shp[-1])
         if k is not None:
@@ -44,11 +44,12 @@ class _RMSNormFn(torch.autograd.Function):
     def backward(ctx, dy: torch.Tensor):
         x2, weight, invrms = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        k = kernels_for(dy2)
+        k = bf16_kernels_for(dy2)
         if k is not None:
             dx, dw = k.rmsnorm_bwd(
                 dy2, x2.contiguous(), _kernel_weight(weight, x2), invrms
             )
+            # the kernel's fp32 sum, rounded once, to the weight's own dtype
             dw = dw.to(weight.dtype)
         else:
             xf = x2.float()

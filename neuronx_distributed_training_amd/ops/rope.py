@@ -11,7 +11,7 @@ from __future__ import annotations
 
 import torch
 
-from . import kernels_for
+from . import bf16_kernels_for
 
 
 def build_rope_cache(
@@ -70,7 +70,7 @@ class _RopeFn(torch.autograd.Function):
         ctx.save_for_backward(cos, sin)
         ctx.pos_offset = pos_offset
         ctx.pos_offset2 = pos_offset2
-        k = kernels_for(x)
+        k = bf16_kernels_for(x)
         if k is not None:
             return k.rope_fwd(x, cos, sin, pos_offset, pos_offset2)
         s = x.size(-2)
@@ -81,7 +81,7 @@ class _RopeFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: torch.Tensor):
         cos, sin = ctx.saved_tensors
-        k = kernels_for(dy)
+        k = bf16_kernels_for(dy)
         if k is not None:
             dx = k.rope_fwd(dy if dy.stride(-1) == 1 else dy.contiguous(),
                             cos, -sin, ctx.pos_offset, ctx.pos_offset2)

@@ -11,11 +11,12 @@ from __future__ import annotations
 import torch
 import torch.nn.functional as F
 
-from . import kernels_for
+from . import bf16_kernels_for
 
 
 def _ref_dtype(t: torch.Tensor) -> torch.dtype:
-    # CPU reference path: fp32 for bf16/fp16/fp32 inputs, fp64 stays fp64
+    # torch path (CPU, and GPU tensors that are not bf16): fp32 for
+    # bf16/fp16/fp32 inputs, fp64 stays fp64
     return torch.promote_types(t.dtype, torch.float32)
 
 
@@ -23,7 +24,7 @@ class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, gate_up: torch.Tensor):
         ctx.save_for_backward(gate_up)
-        k = kernels_for(gate_up)
+        k = bf16_kernels_for(gate_up)
         if k is not None:
             return k.swiglu_fwd(gate_up.reshape(-1, gate_up.size(-1)).contiguous()).reshape(
                 *gate_up.shape[:-1], gate_up.size(-1) // 2
@@ -34,7 +35,7 @@ class _SwiGLUFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy: torch.Tensor):
         (gate_up,) = ctx.saved_tensors
-        k = kernels_for(dy)
+        k = bf16_kernels_for(dy)
         if k is not None:
             d = k.swiglu_bwd(
                 dy.reshape(-1, dy.size(-1)).contiguous(),

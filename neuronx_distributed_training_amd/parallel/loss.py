@@ -39,7 +39,10 @@ class _FusedVocabParallelCrossEntropy(torch.autograd.Function):
         V = logits.size(-1)
         vocab_start = rank * V
         target = target.contiguous()
-        lmax, lsum, tgt = k.ce_fwd(logits.contiguous(), target, vocab_start)
+        # a column slice of a wider buffer reshapes to a strided view; the
+        # copy handed to ce_fwd is the one backward gives to ce_bwd
+        logits = logits.contiguous()
+        lmax, lsum, tgt = k.ce_fwd(logits, target, vocab_start)
         if tp > 1:
             gmax = lmax.clone()
             dist.all_reduce(gmax, op=dist.ReduceOp.MAX, group=group)
