@@ -11,7 +11,12 @@ serve.yaml:
   checkpoint_dir: results/.../checkpoints    # optional (random init if absent)
   tokenizer: meta-llama/Meta-Llama-3-8B      # or "bytes"
   max_new_tokens: 128
+  kv_cache: static        # optional; default "dynamic" (see generate())
   model: {num_layers: 32, hidden_size: 4096, ...}
+
+kv_cache: static preallocates the cache and decodes through the split-KV
+flash-decode kernel; a ragged batch of prompts (left-padded below) then
+keeps its cache instead of being recomputed every token.
 """
 
 from __future__ import annotations
@@ -114,6 +119,7 @@ def create_app(cfg: dict):
             top_k=int(req.get("top_k", 0)),
             top_p=float(req.get("top_p", 0.0)),
             eos_token_id=getattr(tokenizer, "eos_token_id", None),
+            cache_impl=str(cfg.get("kv_cache", "dynamic")),
         )
         texts = [tokenizer.decode(row[width:].tolist()) for row in out]
         n_new = out.size(1) - width

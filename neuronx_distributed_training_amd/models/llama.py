@@ -40,6 +40,7 @@ from ..parallel.mappings import (
 )
 from ..ops import flash_attn_func, swiglu
 from ..ops.flash_attn import mask_to_kv_range_tensors, segment_bounds
+from ..ops.flash_decode import flash_attn_decode
 from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
 from ..ops.rmsnorm import RMSNorm
 
@@ -243,6 +244,30 @@ class LlamaAttention(nn.Module):
             kv_range=kv_range, seg_bounds=seg_bounds,
         )
 
+    def _static_cache_attention(self, q, k, v, cache, layer_idx, kv_range):
+        """Attention under a StaticKVCache: the new K/V are written into the
+        preallocated buffers, which the decode kernel then reads in place.
+        kv_range is the prefill's padding range, None for dense batches."""
+        window = getattr(self.cfg, "sliding_window", None)
+        k_buf, v_buf = cache.update(layer_idx, k, v)
+        s_new, end = q.size(2), cache.seq_len + q.size(2)
+        if cache.seq_len == 0:
+            # prefill (S_q == S_kv): the training forward on the new K/V
+            return flash_attn_func(q, k, v, causal=True, scale=self.scale,
+                                   window=window, kv_range=kv_range)
+        if (self.n_heads_local // self.n_kv_local) * s_new <= 64:
+            return flash_attn_decode(
+                q, k_buf, v_buf, cache.kv_hi, cache.kv_lo, max_kv=end,
+                scale=self.scale, window=window,
+            )
+        # a long chunk after the prefill: more stacked rows than the decode
+        # kernel takes; the ranged forward over a view of the buffers
+        return flash_attn_func(
+            q, k_buf[:, :, :end], v_buf[:, :, :end], causal=True,
+            scale=self.scale, window=window,
+            kv_range=(cache.kv_lo, cache.kv_hi),
+        )
+
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
                 layer_idx: int = 0, pad_mask=None, kv_range=None,
                 seg_bounds=None):
@@ -271,6 +296,9 @@ class LlamaAttention(nn.Module):
                 q, k.repeat_interleave(rep, 1), v.repeat_interleave(rep, 1),
                 attn_mask=am, scale=self.scale,
             )
+        elif isinstance(cache, StaticKVCache):
+            o = self._static_cache_attention(q, k, v, cache, layer_idx,
+                                             kv_range)
         elif cache is not None:
             k, v = cache.update(layer_idx, k, v)
             # prefill (S_q == S_kv) and incremental decode (S_q < S_kv)
@@ -305,6 +333,62 @@ class KVCache:
         else:
             self.k[i] = torch.cat([self.k[i], k], dim=2)
             self.v[i] = torch.cat([self.v[i], v], dim=2)
+        return self.k[i], self.v[i]
+
+
+class StaticKVCache:
+    """Preallocated per-layer K/V buffers [b, hkv, capacity, d], written in
+    place: no allocation and no copy of the past per generated token, and
+    the decode kernel (ops.flash_attn_decode) reads them where they are.
+    Batch row r's keys are positions ``kv_lo[r] <= j < kv_hi[r]``: kv_lo is
+    the row's left padding, fixed by the prefill's attention_mask, and kv_hi
+    the tokens written so far, the same for every row. Both are int32 [b]
+    device tensors, so a decode step needs no mask and no host sync;
+    ``seq_len`` is kv_hi on the host. Buffers are allocated on the first
+    update (dtype and device of the model). Requires SP off and CP == 1."""
+
+    def __init__(self, num_layers: int, batch: int, capacity: int):
+        self.k = [None] * num_layers
+        self.v = [None] * num_layers
+        self.batch = batch
+        self.capacity = capacity
+        self.seq_len = 0
+        self.kv_lo = None
+        self.kv_hi = None
+
+    def begin_step(self, batch: int, s_new: int, device):
+        """Once per model forward, before the layers: checks the step fits
+        and makes kv_hi cover the tokens this forward appends."""
+        if batch != self.batch:
+            raise ValueError(
+                f"StaticKVCache was built for batch {self.batch}, got {batch}"
+            )
+        if self.seq_len + s_new > self.capacity:
+            raise ValueError(
+                f"StaticKVCache capacity {self.capacity} exceeded: "
+                f"{self.seq_len} cached + {s_new} new tokens"
+            )
+        if self.kv_lo is None:
+            self.kv_lo = torch.zeros(batch, dtype=torch.int32, device=device)
+            self.kv_hi = torch.zeros(batch, dtype=torch.int32, device=device)
+        self.kv_hi.fill_(self.seq_len + s_new)
+
+    def update(self, i: int, k: torch.Tensor, v: torch.Tensor):
+        """Write k / v [b, hkv, s_new, d] at [seq_len, seq_len + s_new) of
+        layer i and return the whole buffers."""
+        s_new = k.size(2)
+        end = self.seq_len + s_new
+        if end > self.capacity:
+            raise ValueError(
+                f"StaticKVCache capacity {self.capacity} exceeded: "
+                f"{self.seq_len} cached + {s_new} new tokens"
+            )
+        if self.k[i] is None:
+            shape = (k.size(0), k.size(1), self.capacity, k.size(3))
+            self.k[i] = torch.empty(shape, dtype=k.dtype, device=k.device)
+            self.v[i] = torch.empty(shape, dtype=v.dtype, device=v.device)
+        self.k[i][:, :, self.seq_len:end] = k
+        self.v[i][:, :, self.seq_len:end] = v
         return self.k[i], self.v[i]
 
 
@@ -357,18 +441,25 @@ class LlamaModel(nn.Module):
         """Decide once per forward how a padded batch is attended: returns
         (pad_mask, kv_range), at most one of them set. pad_mask ([b, s]
         bool, True at pad keys) selects the eager SDPA branch; kv_range
-        (int32 kv_lo, kv_hi [b]) the ranged flash kernel. One host sync."""
+        (int32 kv_lo, kv_hi [b]) the ranged flash kernel. One host sync.
+        Under a StaticKVCache the mask is consulted at the prefill only,
+        always as a range (it must be left padding) whose kv_lo the cache
+        keeps for the decode steps; a mask with a hole still runs eager."""
         if attention_mask is None:
             return None, None
         mode = self.cfg.padded_attention
         assert mode in ("auto", "flash", "eager"), \
             f"padded_attention must be auto|flash|eager, got {mode!r}"
-        flash = kv_cache is None and (
+        static = isinstance(kv_cache, StaticKVCache)
+        if static and kv_cache.seq_len > 0:
+            # the prefill's mask fixed kv_lo; decode steps need no mask
+            return None, None
+        flash = (kv_cache is None and (
             mode == "flash"
             or (mode == "auto" and attention_mask.is_cuda
                 and self.cfg.torch_dtype == torch.bfloat16
                 and self.cfg.head_dim in (64, 128))
-        )
+        )) or static
         if not flash:
             if not bool((attention_mask == 0).any()):
                 return None, None
@@ -377,13 +468,24 @@ class LlamaModel(nn.Module):
             return attention_mask == 0, None
         lo, hi, contiguous = mask_to_kv_range_tensors(attention_mask)
         has_pad = (attention_mask == 0).any()
-        has_pad, contiguous = torch.stack([has_pad, contiguous]).tolist()
+        # a static cache appends every row's new tokens at the same index:
+        # only left padding leaves no gap between a row's prompt and them
+        left = (hi == attention_mask.size(1)).all()
+        has_pad, contiguous, left = torch.stack(
+            [has_pad, contiguous, left]).tolist()
         if not has_pad:
             return None, None
         assert ps.get_context_model_parallel_world_size() == 1, \
             "padding masks are not supported under context parallelism"
         if not contiguous:  # a hole inside a row: no range describes it
             return attention_mask == 0, None
+        if static:
+            if not left:
+                raise ValueError(
+                    "a StaticKVCache prefill needs a left-padded "
+                    "attention_mask (every row's ones end at the right edge)"
+                )
+            kv_cache.kv_lo.copy_(lo)
         return None, (lo, hi)
 
     def _segments(self, segment_ids, input_ids, kv_cache):
@@ -430,6 +532,9 @@ class LlamaModel(nn.Module):
         if kv_cache is not None:
             assert not self.cfg.sequence_parallel, "kv cache requires SP off"
             pos_offset = kv_cache.seq_len
+            if isinstance(kv_cache, StaticKVCache):
+                kv_cache.begin_step(input_ids.size(0), input_ids.size(1),
+                                    input_ids.device)
         else:
             from ..parallel.cp import cp_offsets
 

@@ -14,8 +14,9 @@ Kernel inventory (replacing the reference's NKI/apex device stack, SURVEY.md
 §2.3): rmsnorm fwd/bwd, rope fwd/bwd, swiglu fwd/bwd, flash attention
 fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
 sequences, and attention dropout regenerated in-kernel from a counter-based
-keep mask, with a stand-alone mask kernel for tests), vocab-parallel CE
-statistics, fused AdamW(fp32 state).
+keep mask, with a stand-alone mask kernel for tests), split-KV flash decode
+over a preallocated KV cache (forward only), vocab-parallel CE statistics,
+fused AdamW(fp32 state).
 """
 
 from __future__ import annotations
@@ -100,6 +101,7 @@ from .flash_attn import (  # noqa: E402
     mask_to_kv_range,
     segment_bounds,
 )
+from .flash_decode import flash_attn_decode  # noqa: E402
 
 __all__ = [
     "have_extension",
@@ -110,6 +112,7 @@ __all__ = [
     "apply_rotary_pos_emb",
     "swiglu",
     "flash_attn_func",
+    "flash_attn_decode",
     "dropout_keep_mask",
     "dropout_keep_scale",
     "mask_to_kv_range",

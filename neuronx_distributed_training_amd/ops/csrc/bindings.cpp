@@ -513,6 +513,94 @@ std::vector<torch::Tensor> flash_attn_fwd_drop(
                           causal, scale, window, &p_drop, seed, offset);
 }
 
+// Compute units of t's GPU (a host query of a device attribute, no sync).
+static int cu_count(const torch::Tensor& t) {
+  int n = 0;
+  TORCH_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
+                                    t.get_device()) == hipSuccess && n > 0,
+              "cannot read the CU count of GPU ", t.get_device());
+  return n;
+}
+
+// The decode kernel moves q / k / v rows as 16-byte vectors.
+static void check_vec16(const torch::Tensor& t, const char* name) {
+  bool ok = reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  for (int i = 0; i < 3; ++i) ok &= t.size(i) == 1 || t.stride(i) % 8 == 0;
+  TORCH_CHECK(ok, "decode: ", name, " rows must be 16-byte aligned");
+}
+
+// Split-KV decode forward over preallocated cache buffers k / v
+// [B, HKV, CAP, D] (any strides with d contiguous, read in place). Row b sees
+// keys kv_lo[b] <= j < kv_hi[b] <= max_kv (device int32 [B]; the kernel
+// clamps them to [0, max_kv]), bottom-right causal with query i at position
+// kv_hi[b] - S_q + i; what lies outside the range may be NaN and is never
+// read. num_splits <= 0 takes flash_decode_splits (host values and the CU
+// count only: no sync). Returns {O bf16 [B, HQ, S_q, D], LSE fp32
+// [B, HQ, S_q]}; a row with no alive key has O = 0 and LSE = -1e30.
+std::vector<torch::Tensor> flash_attn_decode(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo,
+    torch::Tensor kv_hi, long max_kv, double scale, long window,
+    long num_splits) {
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  check_kv_range(kv_lo, q, "kv_lo");
+  check_kv_range(kv_hi, q, "kv_hi");
+  TORCH_CHECK(k.device() == q.device() && v.device() == q.device(),
+              "decode: k and v must be on the same GPU as q");
+  TORCH_CHECK(k.sizes() == v.sizes(), "decode: k and v shapes differ");
+  check_vec16(q, "q");
+  check_vec16(k, "k");
+  check_vec16(v, "v");
+  FlashDecodeArgs a{};
+  a.B = (int)q.size(0);
+  a.HQ = (int)q.size(1);
+  a.SQ = (int)q.size(2);
+  a.D = (int)q.size(3);
+  a.HKV = (int)k.size(1);
+  const long cap = k.size(2);
+  TORCH_CHECK(a.D == 128 || a.D == 64, "head_dim must be 64 or 128");
+  TORCH_CHECK(k.size(0) == a.B && k.size(3) == a.D,
+              "decode: k / v must be [B, HKV, CAP, D]");
+  TORCH_CHECK(a.HKV > 0 && a.HQ % a.HKV == 0, "GQA head mismatch");
+  TORCH_CHECK(a.B > 0 && a.SQ > 0, "decode: empty q");
+  TORCH_CHECK((long)(a.HQ / a.HKV) * a.SQ <= 64,
+              "decode: (HQ / HKV) * S_q must be <= 64, got ",
+              (long)(a.HQ / a.HKV) * a.SQ, " (use flash_attn_func)");
+  TORCH_CHECK(max_kv >= 1 && max_kv <= cap, "decode: max_kv ", max_kv,
+              " must be in [1, CAP = ", cap, "]");
+  // grid.y / grid.z of the split kernel
+  TORCH_CHECK(a.HKV <= 65535 && a.B <= 65535, "decode: B and HKV <= 65535");
+  TORCH_CHECK(num_splits <= 1024, "decode: num_splits must be <= 1024");
+  a.max_kv = (int)max_kv;
+  a.num_splits =
+      num_splits > 0
+          ? (int)num_splits
+          : flash_decode_splits(a.B, a.HKV, a.max_kv, cu_count(q));
+  a.scale = (float)scale;
+  a.window = (int)window;
+  sbh_strides(q, a.qs);
+  sbh_strides(k, a.ks);
+  sbh_strides(v, a.vs);
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto o = torch::empty({a.B, a.HQ, a.SQ, a.D}, q.options());
+  auto lse = torch::empty({a.B, a.HQ, a.SQ}, f32);
+  // every (split, kv head, batch row) block stores its whole partial
+  auto o_part = torch::empty({a.num_splits, a.B, a.HQ, a.SQ, a.D}, f32);
+  auto lse_part = torch::empty({a.num_splits, a.B, a.HQ, a.SQ}, f32);
+  a.q = q.data_ptr();
+  a.k = k.data_ptr();
+  a.v = v.data_ptr();
+  a.kv_lo = kv_lo.data_ptr<int>();
+  a.kv_hi = kv_hi.data_ptr<int>();
+  a.o = o.data_ptr();
+  a.lse = lse.data_ptr();
+  a.o_part = o_part.data_ptr();
+  a.lse_part = lse_part.data_ptr();
+  launch_flash_decode(a, cur_stream());
+  return {o, lse};
+}
+
 // The keep mask of (p_drop, seed, offset) as uint8 [B, HQ, SQ, SKV] on the
 // current device, 1 = keep: test and debug support, on no hot path.
 torch::Tensor flash_attn_dropout_mask(long B, long HQ, long SQ, long SKV,
@@ -805,6 +893,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("scale"), pybind11::arg("window"),
         pybind11::arg("p_drop"), pybind11::arg("seed"),
         pybind11::arg("offset"));
+  m.def("flash_attn_decode", &flash_attn_decode, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("kv_lo"),
+        pybind11::arg("kv_hi"), pybind11::arg("max_kv"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0,
+        pybind11::arg("num_splits") = 0);
   m.def("flash_attn_dropout_mask", &flash_attn_dropout_mask,
         pybind11::arg("B"), pybind11::arg("HQ"), pybind11::arg("SQ"),
         pybind11::arg("SKV"), pybind11::arg("p_drop"), pybind11::arg("seed"),

@@ -50,7 +50,46 @@ static_assert(flash_block_rows(300, 256) == 256, "512 blocks: 256-row tiles");
 static_assert(flash_block_rows(256, 511) == 128, "511 blocks: 128-row tiles");
 static_assert(flash_block_rows(300, 255) == 128, "510 blocks: 128-row tiles");
 
+// ---- flash decode: argument block and split rule ----
+
+// q is logical [B, HQ, SQ, D] bf16; k / v are the preallocated cache buffers,
+// logical [B, HKV, CAP, D] bf16; d contiguous, stride triples in (seq, batch,
+// head) order as in FlashArgs. Row b sees keys kv_lo[b] <= j < kv_hi[b]
+// (device int32 [B]; the kernel clamps them to [0, max_kv]), bottom-right
+// causal: query i sits at position kv_hi[b] - SQ + i. The grid covers keys
+// [0, max_kv), max_kv <= CAP. o_part / lse_part are fp32 scratch
+// [num_splits, B, HQ, SQ, D] / [num_splits, B, HQ, SQ]; o is bf16
+// [B, HQ, SQ, D] and lse fp32 [B, HQ, SQ], both dense.
+struct FlashDecodeArgs {
+  const void *q, *k, *v;
+  void *o, *lse, *o_part, *lse_part;
+  const int *kv_lo, *kv_hi;
+  int B, HQ, HKV, SQ, D;
+  int max_kv, num_splits;
+  float scale;
+  int window;  // sliding window (<= 0: disabled)
+  long qs[3], ks[3], vs[3];
+};
+
+// Key splits of a decode call, from host values only (never the device
+// lengths: no sync): enough (split, kv head, batch row) blocks for two per
+// CU, at least two 64-key tiles per split, at most 64 splits.
+constexpr int flash_decode_splits(int B, int HKV, int max_kv, int num_cu) {
+  const long base = (long)B * HKV;
+  const long want = (2L * num_cu + base - 1) / base;
+  const long tiles = (max_kv + 63) / 64;
+  const long cap = tiles / 2 < 64 ? tiles / 2 : 64;
+  return (int)(want < cap ? (want < 1 ? 1 : want) : (cap < 1 ? 1 : cap));
+}
+static_assert(flash_decode_splits(1, 8, 8192, 256) == 64, "long, batch 1");
+static_assert(flash_decode_splits(8, 8, 512, 256) == 4, "tile-bound");
+static_assert(flash_decode_splits(64, 8, 4096, 256) == 1, "grid already full");
+static_assert(flash_decode_splits(1, 1, 1, 256) == 1, "one key");
+
 extern "C" {
+// flash_attn_decode.hip: split-KV decode forward, then the combine of the
+// per-split partials
+void launch_flash_decode(const FlashDecodeArgs& a, hipStream_t stream);
 // flash_attn_fwd.hip: single-buffered forward (A/B arm), DENSE only
 void launch_flash_fwd(const FlashArgs& a, hipStream_t stream);
 // flash_attn_fwd_dbuf.hip: double-buffered forward (default), every mask,

@@ -18,23 +18,55 @@ def generate(
     top_p: float = 0.0,
     use_cache: bool = True,
     attention_mask: torch.Tensor | None = None,
+    cache_impl: str = "dynamic",
 ) -> torch.Tensor:
     """input_ids: [b, s]. Returns [b, s + new]. Incremental decode with a
     KV cache when the model supports it (LlamaForCausalLM); full-recompute
-    fallback otherwise."""
+    fallback otherwise.
+
+    cache_impl: "dynamic" = KVCache (grows by torch.cat; a padded batch is
+    recomputed in full every step). "static" = StaticKVCache of capacity
+    s + max_new_tokens, read in place by the flash-decode kernel; it keeps
+    the cache for a LEFT-padded attention_mask too (every row one run of
+    ones ending at the right edge; checked once, one host sync). Any other
+    mask falls back to the full recompute."""
+    if cache_impl not in ("dynamic", "static"):
+        raise ValueError(
+            f"cache_impl must be 'dynamic' or 'static', got {cache_impl!r}"
+        )
     model.eval()
     ids = input_ids
     cache = None
+    can_cache = use_cache and getattr(model, "supports_kv_cache", False) \
+        and not getattr(model.cfg, "sequence_parallel", False)
+    prefill_mask = None
+    if cache_impl == "static" and can_cache and attention_mask is not None:
+        from ..ops.flash_attn import mask_to_kv_range_tensors
+
+        _, hi, contiguous = mask_to_kv_range_tensors(attention_mask)
+        left = contiguous & (hi == attention_mask.size(1)).all()
+        if bool(left):
+            # the prefill turns the mask into the cache's kv_lo; the decode
+            # steps need none
+            prefill_mask, attention_mask = attention_mask, None
     if attention_mask is not None:
         use_cache = False  # padded batch: full recompute honors the mask
     if use_cache and getattr(model, "supports_kv_cache", False) \
             and not getattr(model.cfg, "sequence_parallel", False):
-        from ..models.llama import KVCache
+        from ..models.llama import KVCache, StaticKVCache
 
-        cache = KVCache(len(model.model.layers))
+        if cache_impl == "static":
+            cache = StaticKVCache(len(model.model.layers), ids.size(0),
+                                  ids.size(1) + max_new_tokens)
+        else:
+            cache = KVCache(len(model.model.layers))
     step_in = ids
     for _ in range(max_new_tokens):
-        if cache is not None:
+        if cache is not None and prefill_mask is not None \
+                and cache.seq_len == 0:
+            logits = model(step_in, kv_cache=cache,
+                           attention_mask=prefill_mask)
+        elif cache is not None:
             logits = model(step_in, kv_cache=cache)
         elif attention_mask is not None:
             logits = model(ids, attention_mask=attention_mask)
