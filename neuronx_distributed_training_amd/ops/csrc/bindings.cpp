@@ -425,14 +425,20 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
   return flash_bwd_run(a, dout, q, o, lse, launch_flash_bwd_v3);
 }
 
-// Shared body of the four forward bindings. q/k/v: logical [b, h, s, d],
+// Shared body of the v2 forward bindings. q/k/v: logical [b, h, s, d],
 // arbitrary strides (views of the QKV GEMM output). S_q != S_kv supported;
 // causal is then bottom-right aligned (decode / ring-attention half-block
-// convention, requires S_kv >= S_q). dbuf selects the kernel: true = the
-// double-buffered staging kernel (the default: bit-identical output,
-// measured +3.0% (bench shape) / +1.8% (TP=8 shape)), false = the
-// single-buffered kernel it replaced (flash_attn_fwd_sbuf, kept for A/B;
-// DENSE only).
+// convention, requires S_kv >= S_q). kern selects one of three kernels with
+// bit-identical output:
+//   PIPE  flash_attn_fwd_pipe.hip, the default (flash_attn_fwd, _range,
+//         _seg): swapped-operand S, packed P stores, clamped tile loads,
+//         16-byte O stores. It has no dropout instantiation: its launcher
+//         hands a dropout call to the DBUF kernel.
+//   DBUF  flash_attn_fwd_dbuf.hip, the double-buffered kernel it replaced:
+//         the A/B arm (flash_attn_fwd_dbuf, _range_dbuf, _seg_dbuf) and the
+//         forward of flash_attn_fwd_drop.
+//   SBUF  flash_attn_fwd.hip, the single-buffered kernel before that
+//         (flash_attn_fwd_sbuf, kept for A/B; DENSE only).
 // RANGED: per-batch-row visible key range [kv_lo[b], kv_hi[b]) (padded
 // batches), lo = kv_lo, hi = kv_hi, int32 [B]. Values are trusted to satisfy
 // 0 <= lo <= hi <= S_kv; the Python op clamps them.
@@ -444,8 +450,10 @@ std::vector<torch::Tensor> flash_attn_bwd_v3(torch::Tensor dout,
 // segment ids.
 // p_drop (non-null only from flash_attn_fwd_drop, DENSE): attention dropout
 // on the probabilities with the keep mask of stream (seed, offset).
+enum class FwdKernel { PIPE, DBUF, SBUF };
+
 static std::vector<torch::Tensor> flash_fwd_common(
-    bool dbuf, FlashArgs::Mask mask, torch::Tensor q, torch::Tensor k,
+    FwdKernel kern, FlashArgs::Mask mask, torch::Tensor q, torch::Tensor k,
     torch::Tensor v, const torch::Tensor* lo, const torch::Tensor* hi,
     bool causal, double scale, long window, const double* p_drop = nullptr,
     uint64_t seed = 0, uint64_t offset = 0) {
@@ -469,48 +477,57 @@ static std::vector<torch::Tensor> flash_fwd_common(
   set_mask(a, mask, lo, hi);
   if (p_drop) set_dropout(a, *p_drop, seed, offset);
   return flash_fwd_run(a, q,
-                       dbuf ? launch_flash_fwd_dbuf : launch_flash_fwd);
+                       kern == FwdKernel::PIPE   ? launch_flash_fwd_pipe
+                       : kern == FwdKernel::DBUF ? launch_flash_fwd_dbuf
+                                                 : launch_flash_fwd);
 }
 
-std::vector<torch::Tensor> flash_attn_fwd(torch::Tensor q, torch::Tensor k,
-                                          torch::Tensor v, bool causal,
-                                          double scale, long window) {
-  return flash_fwd_common(true, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
-                          causal, scale, window);
-}
+// The three mask modes of the forward for one kernel arm: SUFFIX "" = the
+// pipe kernel (default), "_dbuf" = the double-buffered kernel (A/B arm).
+#define FLASH_FWD_BINDINGS(SUFFIX, KERN)                                      \
+  std::vector<torch::Tensor> flash_attn_fwd##SUFFIX(                          \
+      torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,         \
+      double scale, long window) {                                            \
+    return flash_fwd_common(KERN, FlashArgs::DENSE, q, k, v, nullptr,         \
+                            nullptr, causal, scale, window);                  \
+  }                                                                           \
+  std::vector<torch::Tensor> flash_attn_fwd_range##SUFFIX(                    \
+      torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo, \
+      torch::Tensor kv_hi, bool causal, double scale, long window) {          \
+    return flash_fwd_common(KERN, FlashArgs::RANGED, q, k, v, &kv_lo, &kv_hi, \
+                            causal, scale, window);                           \
+  }                                                                           \
+  std::vector<torch::Tensor> flash_attn_fwd_seg##SUFFIX(                      \
+      torch::Tensor q, torch::Tensor k, torch::Tensor v,                      \
+      torch::Tensor q_start, torch::Tensor k_end, double scale,               \
+      long window) {                                                          \
+    return flash_fwd_common(KERN, FlashArgs::SEGMENTED, q, k, v, &q_start,    \
+                            &k_end, true, scale, window);                     \
+  }
+FLASH_FWD_BINDINGS(, FwdKernel::PIPE)
+FLASH_FWD_BINDINGS(_dbuf, FwdKernel::DBUF)
+#undef FLASH_FWD_BINDINGS
 
 std::vector<torch::Tensor> flash_attn_fwd_sbuf(torch::Tensor q,
                                                torch::Tensor k,
                                                torch::Tensor v, bool causal,
                                                double scale, long window) {
-  return flash_fwd_common(false, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
-                          causal, scale, window);
-}
-
-std::vector<torch::Tensor> flash_attn_fwd_range(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor kv_lo,
-    torch::Tensor kv_hi, bool causal, double scale, long window) {
-  return flash_fwd_common(true, FlashArgs::RANGED, q, k, v, &kv_lo, &kv_hi,
-                          causal, scale, window);
-}
-
-std::vector<torch::Tensor> flash_attn_fwd_seg(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, torch::Tensor q_start,
-    torch::Tensor k_end, double scale, long window) {
-  return flash_fwd_common(true, FlashArgs::SEGMENTED, q, k, v, &q_start,
-                          &k_end, true, scale, window);
+  return flash_fwd_common(FwdKernel::SBUF, FlashArgs::DENSE, q, k, v, nullptr,
+                          nullptr, causal, scale, window);
 }
 
 // Dense attention with dropout on the probabilities: O = ((P . M) V) *
 // keep_scale with the keep mask M of flash_attn_dropout_mask(.., p_drop,
-// seed, offset); LSE is that of the undropped softmax. t == 0 (p_drop below
-// 1/512) is the dense kernel.
+// seed, offset); LSE is that of the undropped softmax. Always the
+// double-buffered kernel; t == 0 (p_drop below 1/512) is its dense
+// instantiation.
 std::vector<torch::Tensor> flash_attn_fwd_drop(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
     double scale, long window, double p_drop, uint64_t seed,
     uint64_t offset) {
-  return flash_fwd_common(true, FlashArgs::DENSE, q, k, v, nullptr, nullptr,
-                          causal, scale, window, &p_drop, seed, offset);
+  return flash_fwd_common(FwdKernel::DBUF, FlashArgs::DENSE, q, k, v, nullptr,
+                          nullptr, causal, scale, window, &p_drop, seed,
+                          offset);
 }
 
 // Compute units of t's GPU (a host query of a device attribute, no sync).
@@ -882,6 +899,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("o"), pybind11::arg("lse"), pybind11::arg("q_start"),
         pybind11::arg("k_end"), pybind11::arg("scale"),
         pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_dbuf", &flash_attn_fwd_dbuf, pybind11::arg("q"),
+        pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("causal"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_range_dbuf", &flash_attn_fwd_range_dbuf,
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("kv_lo"), pybind11::arg("kv_hi"),
+        pybind11::arg("causal"), pybind11::arg("scale"),
+        pybind11::arg("window") = 0);
+  m.def("flash_attn_fwd_seg_dbuf", &flash_attn_fwd_seg_dbuf,
+        pybind11::arg("q"), pybind11::arg("k"), pybind11::arg("v"),
+        pybind11::arg("q_start"), pybind11::arg("k_end"),
+        pybind11::arg("scale"), pybind11::arg("window") = 0);
   m.def("flash_attn_fwd_drop", &flash_attn_fwd_drop, pybind11::arg("q"),
         pybind11::arg("k"), pybind11::arg("v"), pybind11::arg("causal"),
         pybind11::arg("scale"), pybind11::arg("window"),

@@ -49,7 +49,9 @@ void dispatch_flash(const FlashArgs& a, F&& f) {
 }
 
 // dispatch_flash plus a fifth argument bool_constant<DROPOUT>, for the three
-// kernels with a DROPOUT flag: a.drop_t > 0 adds D x {causal, non-causal}
+// kernels with a DROPOUT flag (the double-buffered forward, dQ, pipelined
+// dK/dV; the pipe forward uses dispatch_flash and leaves dropout calls to the
+// double-buffered one): a.drop_t > 0 adds D x {causal, non-causal}
 // with DROPOUT set, DENSE only (the bindings never set drop_t with another
 // mask mode, and the kernels static_assert against it)
 template <class F>

@@ -35,7 +35,8 @@ struct FlashArgs {
   const int *bound_a, *bound_b;
   // Attention dropout (attn_dropout.h), DENSE only: drop_t = round(256 * p)
   // in 1..255 selects the DROPOUT instantiations of the double-buffered
-  // forward, the dQ kernel and the pipelined dK/dV kernel; 0 = no dropout
+  // forward (the pipe forward has none and hands such calls to it), the dQ
+  // kernel and the pipelined dK/dV kernel; 0 = no dropout
   // (every other call). (drop_seed, drop_offset) name the random stream.
   int drop_t;
   unsigned long long drop_seed, drop_offset;
@@ -92,9 +93,13 @@ extern "C" {
 void launch_flash_decode(const FlashDecodeArgs& a, hipStream_t stream);
 // flash_attn_fwd.hip: single-buffered forward (A/B arm), DENSE only
 void launch_flash_fwd(const FlashArgs& a, hipStream_t stream);
-// flash_attn_fwd_dbuf.hip: double-buffered forward (default), every mask,
-// dropout
+// flash_attn_fwd_dbuf.hip: double-buffered forward, every mask, dropout; the
+// A/B arm of the pipe kernel and the forward of every dropout call
 void launch_flash_fwd_dbuf(const FlashArgs& a, hipStream_t stream);
+// flash_attn_fwd_pipe.hip: swapped-operand forward (default), every mask,
+// bit-equal to the dbuf kernel; a dropout call (drop_t > 0) is handed to
+// launch_flash_fwd_dbuf
+void launch_flash_fwd_pipe(const FlashArgs& a, hipStream_t stream);
 // flash_attn_bwd.hip: dK/dV, then dQ. pipe = true: dK/dV by the pipelined
 // kernel (default); false: by flash_bwd_dkv_kernel (A/B arm, bit-equal).
 // A dropout call (drop_t > 0) always takes the pipelined kernel.

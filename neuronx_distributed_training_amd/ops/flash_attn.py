@@ -43,7 +43,8 @@ from . import kernels_for
 
 
 def _attn_version() -> str:
-    """Kernel generation: '2' = 16x16x32 MFMA 8-wave (default), '3' =
+    """Kernel generation: '2' = 16x16x32 MFMA 8-wave (default; its forward
+    is one of the two bit-identical kernels of :func:`_fwd_arm`), '3' =
     32x32x16 swapped-operand register-softmax, 'fwd' = v3 forward with v2
     backward (r2 A/B: v3 end-to-end measured slower than v2).
     NXDT_ATTN_V3=1/0/fwd overrides."""
@@ -55,12 +56,33 @@ def _attn_version() -> str:
     return "2"
 
 
+def _fwd_arm() -> str:
+    """Forward kernel of the v2 path: 'pipe' = the swapped-operand kernel
+    (flash_attn_fwd_pipe.hip, default), 'dbuf' = the double-buffered kernel
+    it replaced, kept for A/B; the two are bit-identical.
+    NXDT_ATTN_FWD=pipe/dbuf overrides. (Dropout calls run the dbuf kernel
+    under either value: the pipe kernel has no dropout instantiation. The
+    single-buffered kernel before both is only reachable as the
+    ``flash_attn_fwd_sbuf`` binding.)"""
+    env = os.environ.get("NXDT_ATTN_FWD", "") or "pipe"
+    if env not in ("pipe", "dbuf"):
+        raise ValueError(f"NXDT_ATTN_FWD must be 'pipe' or 'dbuf', got {env!r}")
+    return env
+
+
+def v2_fwd_fn(kern, kind=""):
+    """The v2 forward binding of `kind` ('' dense, '_range', '_seg') for
+    the forward arm NXDT_ATTN_FWD selects."""
+    suffix = "_dbuf" if _fwd_arm() == "dbuf" else ""
+    return getattr(kern, f"flash_attn_fwd{kind}{suffix}")
+
+
 def _fwd_fn(kern, sq=None, skv=None):
     # v3 covers the training shape (S_q == S_kv); decode / ring half-blocks
     # (S_q != S_kv) always go through v2, which supports them.
     if _attn_version() in ("3", "fwd") and (sq is None or sq == skv):
         return kern.flash_attn_fwd_v3
-    return kern.flash_attn_fwd
+    return v2_fwd_fn(kern)
 
 
 def _dkv_arm() -> str:
@@ -307,18 +329,19 @@ class _FlashAttnFn(torch.autograd.Function):
         ranged = kv_lo is not None
         segmented = q_start is not None
         if kern is not None and drop is not None:
-            # dropout calls always use the v2 kernels
+            # dropout calls always use the v2 kernels, and of the v2
+            # forwards the double-buffered one, whatever NXDT_ATTN_FWD says
             o, lse = kern.flash_attn_fwd_drop(
                 q, k, v, causal, scale, window, *drop
             )
         elif kern is not None and segmented:
             # segmented calls always use the v2 kernels too
-            o, lse = kern.flash_attn_fwd_seg(
+            o, lse = v2_fwd_fn(kern, "_seg")(
                 q, k, v, q_start, k_end, scale, window
             )
         elif kern is not None and ranged:
             # ranged calls always use the v2 kernels (like S_q != S_kv)
-            o, lse = kern.flash_attn_fwd_range(
+            o, lse = v2_fwd_fn(kern, "_range")(
                 q, k, v, kv_lo, kv_hi, causal, scale, window
             )
         elif kern is not None:

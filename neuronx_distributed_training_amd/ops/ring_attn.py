@@ -38,7 +38,8 @@ import torch
 import torch.distributed as dist
 
 from ..parallel import state as ps
-from .flash_attn import _FlashAttnFn, _cpu_ref_fwd, _make_mask, v2_bwd_fn
+from .flash_attn import (_FlashAttnFn, _cpu_ref_fwd, _make_mask, v2_bwd_fn,
+                         v2_fwd_fn)
 from . import kernels_for
 
 
@@ -63,7 +64,7 @@ def _post_shift(send_tensors, recv_buffers):
 
 def _fwd_block(kern, q, k, v, causal, scale):
     if kern is not None:
-        o, lse = kern.flash_attn_fwd(q, k, v, causal, scale)
+        o, lse = v2_fwd_fn(kern)(q, k, v, causal, scale)
         return o, lse
     return _cpu_ref_fwd(q, k, v, causal, scale)
 
