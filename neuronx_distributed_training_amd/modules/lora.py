@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..ops.lora import lora_delta_add
 from ..parallel.layers import ColumnParallelLinear, RowParallelLinear
 from ..parallel.mappings import (
     copy_to_tensor_model_parallel_region,
@@ -91,15 +92,15 @@ class LoRAColumnParallelLinear(nn.Module):
             out = F.linear(xg, b.weight, b.bias)
             # delta rides the SAME mapped input so its dx contribution is
             # reduced over TP exactly once in backward
-            delta_in = self.dropout(xg)
-            out = out + F.linear(F.linear(delta_in, self.lora_A), self.lora_B) * self.scaling
+            out = lora_delta_add(out, self.dropout(xg), self.lora_A,
+                                 self.lora_B, self.scaling)
             if b.gather_output:
                 from ..parallel.mappings import gather_from_tensor_model_parallel_region
                 out = gather_from_tensor_model_parallel_region(out)
             return out
         # RowParallel: add the low-rank partial before the reduction
-        out = F.linear(x, b.weight)
-        out = out + F.linear(F.linear(self.dropout(x), self.lora_A), self.lora_B) * self.scaling
+        out = lora_delta_add(F.linear(x, b.weight), self.dropout(x),
+                             self.lora_A, self.lora_B, self.scaling)
         if b.sequence_parallel:
             out = reduce_scatter_to_sequence_parallel_region(out)
         else:

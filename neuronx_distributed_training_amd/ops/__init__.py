@@ -16,7 +16,9 @@ fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
 sequences, and attention dropout regenerated in-kernel from a counter-based
 keep mask, with a stand-alone mask kernel for tests), split-KV flash decode
 over a preallocated KV cache (forward only), vocab-parallel CE statistics,
-fused AdamW(fp32 state).
+fused AdamW(fp32 state), grouped MoE expert GEMMs, and the LoRA adapter
+products (skinny shrink, expand-add fused with the base output, two-stage
+wgrad; bf16, r in 8/16/32/64).
 """
 
 from __future__ import annotations
@@ -102,6 +104,7 @@ from .flash_attn import (  # noqa: E402
     segment_bounds,
 )
 from .flash_decode import flash_attn_decode  # noqa: E402
+from .lora import lora_delta_add  # noqa: E402
 
 __all__ = [
     "have_extension",
@@ -113,6 +116,7 @@ __all__ = [
     "swiglu",
     "flash_attn_func",
     "flash_attn_decode",
+    "lora_delta_add",
     "dropout_keep_mask",
     "dropout_keep_scale",
     "mask_to_kv_range",

@@ -786,6 +786,87 @@ torch::Tensor moe_wgrad(torch::Tensor dy, torch::Tensor x,
   return dw;
 }
 
+// ---- LoRA adapter products (lora.hip) ----
+// The kernels index dense row-major bf16 with 16-byte row vectors and have
+// one instantiation per rank, so rank, dtype and alignment are settled here.
+static void check_lora_rank(long r, const char* op) {
+  TORCH_CHECK(r == 8 || r == 16 || r == 32 || r == 64, op,
+              ": rank must be 8, 16, 32 or 64, got ", r);
+}
+
+// A wide operand [T, W] and a rank-r one ([r, W] or [T, r]).
+static void check_lora_pair(const torch::Tensor& wide,
+                            const torch::Tensor& skinny, const char* op) {
+  check_dense(wide, wide, torch::kBFloat16, op, "the wide operand");
+  check_dense(skinny, wide, torch::kBFloat16, op, "the rank-r operand");
+  TORCH_CHECK(wide.dim() == 2 && skinny.dim() == 2, op,
+              ": operands must be 2-D");
+  TORCH_CHECK(wide.size(0) < (1L << 31) && wide.size(1) < (1L << 31), op,
+              ": sizes must be below 2^31");
+  TORCH_CHECK(wide.size(1) > 0 && wide.size(1) % 8 == 0, op,
+              ": the wide dimension must be a positive multiple of 8, got ",
+              wide.size(1));
+}
+
+// h[T, r] = scale * x[T, W] @ m[r, W]^T, rounded once.
+torch::Tensor lora_shrink(torch::Tensor x, torch::Tensor m, double scale) {
+  check_lora_pair(x, m, "lora_shrink");
+  const long T = x.size(0), W = x.size(1), R = m.size(0);
+  check_lora_rank(R, "lora_shrink");
+  TORCH_CHECK(m.size(1) == W, "lora_shrink: m must be [r, ", W, "]");
+  auto h = torch::empty({T, R}, x.options());
+  launch_lora_shrink(x.data_ptr(), m.data_ptr(), h.data_ptr(), (int)T, (int)W,
+                     (int)R, (float)scale, cur_stream());
+  return h;
+}
+
+// out[T, N] = (base +) scale * h[T, r] @ m[N, r]^T, rounded once from the
+// fp32 sum.
+torch::Tensor lora_expand(torch::Tensor h, torch::Tensor m, double scale,
+                          c10::optional<torch::Tensor> base) {
+  check_dense(h, h, torch::kBFloat16, "lora_expand", "h");
+  check_dense(m, h, torch::kBFloat16, "lora_expand", "m");
+  TORCH_CHECK(h.dim() == 2 && m.dim() == 2, "lora_expand: h and m must be 2-D");
+  const long T = h.size(0), R = h.size(1), N = m.size(0);
+  check_lora_rank(R, "lora_expand");
+  TORCH_CHECK(m.size(1) == R, "lora_expand: m must be [N, ", R, "]");
+  TORCH_CHECK(N > 0 && N % 8 == 0,
+              "lora_expand: N must be a positive multiple of 8, got ", N);
+  // grid.y covers N in 64-column tiles
+  TORCH_CHECK(T < (1L << 31) && N <= 64L * 65535, "lora_expand: too large");
+  const void* bp = nullptr;
+  if (base.has_value()) {
+    check_dense(*base, h, torch::kBFloat16, "lora_expand", "base");
+    TORCH_CHECK(base->dim() == 2 && base->size(0) == T && base->size(1) == N,
+                "lora_expand: base must be [", T, ", ", N, "]");
+    bp = base->data_ptr();
+  }
+  auto out = torch::empty({T, N}, h.options());
+  launch_lora_expand(h.data_ptr(), m.data_ptr(), bp, out.data_ptr(), (int)T,
+                     (int)N, (int)R, (float)scale, cur_stream());
+  return out;
+}
+
+// g = scale * y[T, W]^T @ z[T, r] as bf16 [W, r], or [r, W] when out_rw: the
+// layouts of lora_B and lora_A. T == 0 gives zeros.
+torch::Tensor lora_wgrad(torch::Tensor y, torch::Tensor z, double scale,
+                         bool out_rw) {
+  check_lora_pair(y, z, "lora_wgrad");
+  const long T = y.size(0), W = y.size(1), R = z.size(1);
+  check_lora_rank(R, "lora_wgrad");
+  TORCH_CHECK(z.size(0) == T, "lora_wgrad: y and z row counts differ");
+  TORCH_CHECK(lora_wgrad_chunks(T) <= 65535, "lora_wgrad: too many rows");
+  // every block stores its whole [64, r] part of its chunk's slab
+  auto part = torch::empty({lora_wgrad_chunks(T), W, R},
+                           y.options().dtype(torch::kFloat32));
+  auto g = out_rw ? torch::empty({R, W}, y.options())
+                  : torch::empty({W, R}, y.options());
+  launch_lora_wgrad(y.data_ptr(), z.data_ptr(), part.data_ptr(), g.data_ptr(),
+                    (int)T, (int)W, (int)R, (float)scale, out_rw,
+                    cur_stream());
+  return g;
+}
+
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a);
   CHECK_IN(b);
@@ -959,4 +1040,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("moe_gemm", &moe_gemm);
   m.def("moe_wgrad", &moe_wgrad);
+  m.def("lora_shrink", &lora_shrink, py::arg("x"), py::arg("m"),
+        py::arg("scale") = 1.0);
+  m.def("lora_expand", &lora_expand, py::arg("h"), py::arg("m"),
+        py::arg("scale") = 1.0, py::arg("base") = py::none());
+  m.def("lora_wgrad", &lora_wgrad, py::arg("y"), py::arg("z"),
+        py::arg("scale") = 1.0, py::arg("out_rw") = false);
 }

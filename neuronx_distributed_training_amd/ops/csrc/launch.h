@@ -87,7 +87,31 @@ static_assert(flash_decode_splits(8, 8, 512, 256) == 4, "tile-bound");
 static_assert(flash_decode_splits(64, 8, 4096, 256) == 1, "grid already full");
 static_assert(flash_decode_splits(1, 1, 1, 256) == 1, "one key");
 
+// ---- LoRA adapter products (lora.hip) ----
+
+// Rows of T that one block of the wgrad kernel contracts; the second stage
+// sums the ceil(T / chunk) fp32 partial slabs in chunk order.
+constexpr int LORA_WGRAD_CHUNK = 256;
+constexpr int lora_wgrad_chunks(long T) {
+  return (int)((T + LORA_WGRAD_CHUNK - 1) / LORA_WGRAD_CHUNK);
+}
+static_assert(lora_wgrad_chunks(0) == 0 && lora_wgrad_chunks(257) == 2,
+              "no rows: no partial; a ragged last chunk counts");
+
 extern "C" {
+// lora.hip: all tensors dense row-major bf16, R in {8, 16, 32, 64}, W and N
+// multiples of 8. shrink: h[T, R] = scale * x[T, W] m[R, W]^T. expand:
+// out[T, N] = (base[T, N] +) scale * h[T, R] m[N, R]^T, base may be null.
+// wgrad: g = scale * y[T, W]^T z[T, R], written as [W, R], or as [R, W] when
+// out_rw; part is fp32 scratch [lora_wgrad_chunks(T), W, R].
+void launch_lora_shrink(const void* x, const void* m, void* h, int T, int W,
+                        int R, float scale, hipStream_t stream);
+void launch_lora_expand(const void* h, const void* m, const void* base,
+                        void* out, int T, int N, int R, float scale,
+                        hipStream_t stream);
+void launch_lora_wgrad(const void* y, const void* z, void* part, void* g,
+                       int T, int W, int R, float scale, bool out_rw,
+                       hipStream_t stream);
 // flash_attn_decode.hip: split-KV decode forward, then the combine of the
 // per-split partials
 void launch_flash_decode(const FlashDecodeArgs& a, hipStream_t stream);

@@ -36,6 +36,7 @@ sources = [
         "attn_dropout.hip",
         "cross_entropy.hip",
         "moe_gemm.hip",
+        "lora.hip",
         "probe.hip",
     )
 ]
