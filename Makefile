@@ -1,7 +1,7 @@
 # Convenience targets (see docs/general/installation_guide.md)
 PY ?= python
 
-.PHONY: build test test-gpu bench smoke parity bench-attn bench-dkv bench-fwd bench-decode family-smoke clean
+.PHONY: build test test-gpu bench smoke parity bench-attn bench-dkv bench-fwd bench-decode bench-lm-head family-smoke clean
 
 build:
 	PYTORCH_ROCM_ARCH=gfx950 $(PY) setup.py build_ext --inplace
@@ -33,6 +33,9 @@ bench-fwd:
 
 bench-decode:
 	$(PY) tools/bench_decode.py
+
+bench-lm-head:
+	$(PY) tools/bench_lm_head_loss.py
 
 family-smoke:
 	$(PY) tools/gpu_family_smoke.py

@@ -32,8 +32,12 @@ from ..parallel.layers import (
     ParallelEmbedding,
     RowParallelLinear,
 )
-from ..parallel.loss import parallel_cross_entropy
+from ..parallel.loss import (
+    parallel_cross_entropy,
+    parallel_linear_cross_entropy,
+)
 from ..parallel.mappings import (
+    copy_to_tensor_model_parallel_region,
     gather_from_tensor_model_parallel_region,
     gather_from_sequence_parallel_region,
     scatter_to_sequence_parallel_region,
@@ -72,6 +76,10 @@ class LlamaConfig:
     # head_dim 64/128, else "eager". A mask with holes inside a row always
     # runs "eager".
     padded_attention: str = "auto"
+    # loss straight from the final hidden states and lm_head.weight
+    # (parallel_linear_cross_entropy): the [tokens, vocab] logits are never
+    # held. Only the forward with labels; off by default.
+    fused_lm_head_loss: bool = False
     dtype: str = "float32"
 
     @property
@@ -586,20 +594,35 @@ class LlamaForCausalLM(nn.Module):
         hidden = self.model(input_ids, kv_cache=kv_cache,
                             attention_mask=attention_mask,
                             segment_ids=segment_ids)
+        fused = self.cfg.fused_lm_head_loss and labels is not None
         # under SP the model's output gather already provides the TP input
         # mapping (backward reduce-scatter); pre_mapped skips the copy so
         # the reduction isn't applied twice
-        logits = self.lm_head(hidden, pre_mapped=self.cfg.sequence_parallel)
-        if labels is None:
-            return gather_from_tensor_model_parallel_region(logits)
+        if fused:
+            # the input mapping of ColumnParallelLinear.forward, lm_head
+            # itself skipped: the loss op reads its weight
+            if not self.cfg.sequence_parallel:
+                hidden = copy_to_tensor_model_parallel_region(hidden)
+        else:
+            logits = self.lm_head(hidden,
+                                  pre_mapped=self.cfg.sequence_parallel)
+            if labels is None:
+                return gather_from_tensor_model_parallel_region(logits)
         cp = ps.get_context_model_parallel_world_size()
         if cp == 1:
             # next-token shift (under CP the split batches are pre-shifted;
             # reference skips the logit shift at modeling_llama.py:817-819)
-            logits = logits[:, :-1]
+            if fused:
+                hidden = hidden[:, :-1]
+            else:
+                logits = logits[:, :-1]
             labels = labels[:, 1:]
             loss_mask = loss_mask[:, 1:] if loss_mask is not None else None
-        per_tok = parallel_cross_entropy(logits, labels)
+        if fused:
+            per_tok = parallel_linear_cross_entropy(
+                hidden, self.lm_head.weight, labels)
+        else:
+            per_tok = parallel_cross_entropy(logits, labels)
         if loss_mask is not None:
             m = loss_mask.to(per_tok.dtype)
             denom = (loss_denominator if loss_denominator is not None

@@ -16,9 +16,12 @@ fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
 sequences, and attention dropout regenerated in-kernel from a counter-based
 keep mask, with a stand-alone mask kernel for tests), split-KV flash decode
 over a preallocated KV cache (forward only), vocab-parallel CE statistics,
-fused AdamW(fp32 state), grouped MoE expert GEMMs, and the LoRA adapter
+fused AdamW(fp32 state), grouped MoE expert GEMMs, the LoRA adapter
 products (skinny shrink, expand-add fused with the base output, two-stage
-wgrad; bf16, r in 8/16/32/64).
+wgrad; bf16, r in 8/16/32/64), and the fused LM-head + cross-entropy (the
+NT MFMA GEMM hidden @ lm_head^T with the softmax statistics, or the logit
+gradient of a row chunk, as its epilogue: the [tokens, vocab] logits are
+never stored; opt-in, model.fused_lm_head_loss).
 """
 
 from __future__ import annotations
@@ -105,6 +108,7 @@ from .flash_attn import (  # noqa: E402
 )
 from .flash_decode import flash_attn_decode  # noqa: E402
 from .lora import lora_delta_add  # noqa: E402
+from .lm_head_loss import linear_cross_entropy  # noqa: E402
 
 __all__ = [
     "have_extension",
@@ -117,6 +121,7 @@ __all__ = [
     "flash_attn_func",
     "flash_attn_decode",
     "lora_delta_add",
+    "linear_cross_entropy",
     "dropout_keep_mask",
     "dropout_keep_scale",
     "mask_to_kv_range",

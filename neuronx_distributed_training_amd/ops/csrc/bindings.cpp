@@ -867,6 +867,77 @@ torch::Tensor lora_wgrad(torch::Tensor y, torch::Tensor z, double scale,
   return g;
 }
 
+// ---- fused LM-head + cross-entropy (lm_head_loss.hip) ----
+// The kernels index dense row-major bf16 [N, H] / [V, H] with 16-byte vectors
+// along H and walk H in whole LMHEAD_BK steps; dS rows are stored as 16-byte
+// vectors, so V % 8 == 0.
+static void check_lmhead(const torch::Tensor& hidden,
+                         const torch::Tensor& weight,
+                         const torch::Tensor& targets, const char* op) {
+  check_dense(hidden, hidden, torch::kBFloat16, op, "hidden");
+  check_dense(weight, hidden, torch::kBFloat16, op, "weight");
+  TORCH_CHECK(hidden.dim() == 2 && weight.dim() == 2 &&
+                  weight.size(1) == hidden.size(1),
+              op, ": hidden must be [N, H] and weight [V, H]");
+  const long N = hidden.size(0), H = hidden.size(1), V = weight.size(0);
+  TORCH_CHECK(H > 0 && H % LMHEAD_BK == 0, op, ": H must be a positive ",
+              "multiple of ", LMHEAD_BK, ", got ", H);
+  TORCH_CHECK(V > 0 && V % 8 == 0, op,
+              ": V must be a positive multiple of 8, got ", V);
+  TORCH_CHECK(V < (1L << 31) && H < (1L << 31) &&
+                  lmhead_tiles(N, LMHEAD_BM) * lmhead_vtiles(V) < (1L << 31),
+              op, ": too large for one grid");
+  check_vec(targets, hidden, torch::kLong, N, op, "targets");
+}
+
+// {row_max, row_sumexp, tgt_logit} fp32 [N] of the logits hidden @ weight^T,
+// the three outputs of ce_fwd, without the logits.
+std::vector<torch::Tensor> lmhead_ce_fwd(torch::Tensor hidden,
+                                         torch::Tensor weight,
+                                         torch::Tensor targets,
+                                         long vocab_start) {
+  check_lmhead(hidden, weight, targets, "lmhead_ce_fwd");
+  const long N = hidden.size(0), H = hidden.size(1), V = weight.size(0);
+  auto f32 = hidden.options().dtype(torch::kFloat32);
+  const int n_vt = lmhead_vtiles(V);
+  // every (row, vocab tile) pair is written; tgt only where the shard owns
+  // the target
+  auto part = torch::empty({N, n_vt, 2}, f32);
+  auto row_max = torch::empty({N}, f32);
+  auto row_sumexp = torch::empty({N}, f32);
+  auto tgt = torch::zeros({N}, f32);
+  launch_lmhead_ce_fwd(hidden.data_ptr(), weight.data_ptr(),
+                       targets.data_ptr(), part.data_ptr(), tgt.data_ptr(), N,
+                       (int)H, (int)V, vocab_start, cur_stream());
+  launch_lmhead_ce_merge(part.data_ptr(), row_max.data_ptr(),
+                         row_sumexp.data_ptr(), N, n_vt, cur_stream());
+  return {row_max, row_sumexp, tgt};
+}
+
+// dS of rows [r0, r0 + rows) into the first `rows` rows of ds [>= rows, V].
+void lmhead_ce_dlogits(torch::Tensor hidden, torch::Tensor weight,
+                       torch::Tensor targets, torch::Tensor gmax,
+                       torch::Tensor gsum, torch::Tensor gout,
+                       long vocab_start, long r0, long rows,
+                       torch::Tensor ds) {
+  check_lmhead(hidden, weight, targets, "lmhead_ce_dlogits");
+  const long N = hidden.size(0), H = hidden.size(1), V = weight.size(0);
+  check_vec(gmax, hidden, torch::kFloat32, N, "lmhead_ce_dlogits", "gmax");
+  check_vec(gsum, hidden, torch::kFloat32, N, "lmhead_ce_dlogits", "gsum");
+  check_vec(gout, hidden, torch::kFloat32, N, "lmhead_ce_dlogits", "gout");
+  check_dense(ds, hidden, torch::kBFloat16, "lmhead_ce_dlogits", "ds");
+  TORCH_CHECK(r0 >= 0 && rows >= 0 && r0 + rows <= N,
+              "lmhead_ce_dlogits: rows [", r0, ", ", r0 + rows,
+              ") outside [0, ", N, ")");
+  TORCH_CHECK(ds.dim() == 2 && ds.size(0) >= rows && ds.size(1) == V,
+              "lmhead_ce_dlogits: ds must be [>= ", rows, ", ", V, "]");
+  launch_lmhead_ce_dlogits(
+      hidden.data_ptr<at::BFloat16>() + r0 * H, weight.data_ptr(),
+      targets.data_ptr<int64_t>() + r0, gmax.data_ptr<float>() + r0,
+      gsum.data_ptr<float>() + r0, gout.data_ptr<float>() + r0,
+      ds.data_ptr(), rows, (int)H, (int)V, vocab_start, cur_stream());
+}
+
 torch::Tensor mfma_probe(torch::Tensor a, torch::Tensor b) {
   CHECK_IN(a);
   CHECK_IN(b);
@@ -1046,4 +1117,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale") = 1.0, py::arg("base") = py::none());
   m.def("lora_wgrad", &lora_wgrad, py::arg("y"), py::arg("z"),
         py::arg("scale") = 1.0, py::arg("out_rw") = false);
+  m.def("lmhead_ce_fwd", &lmhead_ce_fwd, py::arg("hidden"), py::arg("weight"),
+        py::arg("targets"), py::arg("vocab_start"));
+  m.def("lmhead_ce_dlogits", &lmhead_ce_dlogits, py::arg("hidden"),
+        py::arg("weight"), py::arg("targets"), py::arg("gmax"),
+        py::arg("gsum"), py::arg("gout"), py::arg("vocab_start"),
+        py::arg("r0"), py::arg("rows"), py::arg("ds"));
+  m.attr("LMHEAD_BM") = LMHEAD_BM;
+  m.attr("LMHEAD_BK") = LMHEAD_BK;
 }

@@ -98,7 +98,35 @@ constexpr int lora_wgrad_chunks(long T) {
 static_assert(lora_wgrad_chunks(0) == 0 && lora_wgrad_chunks(257) == 2,
               "no rows: no partial; a ragged last chunk counts");
 
+// ---- fused LM-head + cross-entropy (lm_head_loss.hip) ----
+
+// Token rows and vocab columns of one block's logits tile, and the step of
+// its K loop over H.
+constexpr int LMHEAD_BM = 128, LMHEAD_BN = 128, LMHEAD_BK = 64;
+constexpr long lmhead_tiles(long n, int tile) { return (n + tile - 1) / tile; }
+constexpr int lmhead_vtiles(long V) { return (int)lmhead_tiles(V, LMHEAD_BN); }
+static_assert(lmhead_vtiles(128) == 1 && lmhead_vtiles(136) == 2,
+              "one 8-column group past a tile is a tile of its own");
+
 extern "C" {
+// lm_head_loss.hip: hidden [N, H] and weight [V, H] dense bf16, H % LMHEAD_BK
+// == 0, V % 8 == 0; targets int64 global ids; the shard owns ids
+// [vocab_start, vocab_start + V). fwd: part[N, lmhead_vtiles(V)] float2 (max,
+// sum-exp at that max) per row and vocab tile, and tgt[N] fp32, ZERO on entry,
+// the target logit of the rows whose target the shard owns. merge: part ->
+// row_max / row_sumexp [N] fp32, the outputs of launch_ce_fwd. dlogits: for
+// `rows` rows (all row pointers already offset to the chunk), ds[rows, V]
+// bf16 = (exp(logit - gmax) / gsum - onehot) * gout.
+void launch_lmhead_ce_fwd(const void* hidden, const void* weight,
+                          const void* targets, void* part, void* tgt, long N,
+                          int H, int V, long vocab_start, hipStream_t stream);
+void launch_lmhead_ce_merge(const void* part, void* row_max, void* row_sumexp,
+                            long N, int n_vt, hipStream_t stream);
+void launch_lmhead_ce_dlogits(const void* hidden, const void* weight,
+                              const void* targets, const void* gmax,
+                              const void* gsum, const void* gout, void* ds,
+                              long rows, int H, int V, long vocab_start,
+                              hipStream_t stream);
 // lora.hip: all tensors dense row-major bf16, R in {8, 16, 32, 64}, W and N
 // multiples of 8. shrink: h[T, R] = scale * x[T, W] m[R, W]^T. expand:
 // out[T, N] = (base[T, N] +) scale * h[T, R] m[N, R]^T, base may be null.

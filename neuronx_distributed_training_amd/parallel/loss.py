@@ -11,6 +11,8 @@ d(loss)/d(logits) = softmax - onehot, computed shard-locally.
 On GPU the softmax statistics run through the fused HIP kernel when the
 logits are TP-local and bf16/fp32 (ops.cross_entropy); this module is the
 collective-aware wrapper and the CPU/gloo reference path.
+``parallel_linear_cross_entropy`` takes the hidden states and the lm_head
+weight instead of the logits and never holds them (ops/lm_head_loss.py).
 """
 
 from __future__ import annotations
@@ -20,7 +22,11 @@ import torch.distributed as dist
 
 from . import state as ps
 
-__all__ = ["parallel_cross_entropy", "from_parallel_logits_to_logprobs"]
+__all__ = [
+    "parallel_cross_entropy",
+    "parallel_linear_cross_entropy",
+    "from_parallel_logits_to_logprobs",
+]
 
 
 class _FusedVocabParallelCrossEntropy(torch.autograd.Function):
@@ -156,6 +162,34 @@ def parallel_cross_entropy(
             flat_logits, flat_target, label_smoothing
         )
     return loss.reshape(target.shape)
+
+
+def parallel_linear_cross_entropy(
+    hidden: torch.Tensor, weight: torch.Tensor, target: torch.Tensor,
+    chunk_rows=None,
+) -> torch.Tensor:
+    """Per-token CE loss of the vocab-sharded logits ``hidden @ weight^T``
+    without holding them: hidden [..., H], weight [vocab/tp, H] (the lm_head
+    layout), target [...] global ids; returns the loss in target's shape.
+
+    bf16 GPU tensors with H % 64 == 0, vocab/tp % 8 == 0 and at least one
+    token run the fused HIP kernels (ops/lm_head_loss.py); the backward
+    recomputes the logits in chunks of ``chunk_rows`` rows (default: an eighth
+    of the rows, rounded up to the kernel's 128-row tile). Anything else, CPU
+    included, evaluates ``parallel_cross_entropy(F.linear(hidden, weight),
+    target)``.
+    """
+    from ..ops.lm_head_loss import fused_path_supported, linear_cross_entropy
+
+    if not fused_path_supported(hidden, weight):
+        return parallel_cross_entropy(
+            torch.nn.functional.linear(hidden, weight), target
+        )
+    loss = linear_cross_entropy(
+        hidden.reshape(-1, hidden.size(-1)), weight, target.reshape(-1),
+        chunk_rows,
+    )
+    return loss if target.dim() == 1 else loss.view(target.shape)
 
 
 def from_parallel_logits_to_logprobs(

@@ -330,6 +330,7 @@ class LlamaModule(BaseModelModule):
             sliding_window=mcfg.get("sliding_window"),
             padded_attention=str(mcfg.get("padded_attention", "auto")),
             tie_word_embeddings=bool(mcfg.get("tie_word_embeddings", False)),
+            fused_lm_head_loss=bool(mcfg.get("fused_lm_head_loss", False)),
             dtype=dtype,
         )
         if ps.get_pipeline_model_parallel_world_size() > 1:

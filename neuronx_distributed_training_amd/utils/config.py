@@ -92,6 +92,13 @@ def validate_config(cfg: Dict):
         # SP meaningless at TP=1; force off (reference megatron_base_model.py:76-80)
         ds["sequence_parallel"] = False
     model = cfg.get("model", {})
+    # model.fused_lm_head_loss -> LlamaConfig.fused_lm_head_loss, false when
+    # absent. A YAML bool only: the string "false" would be truthy
+    fused = model.get("fused_lm_head_loss", False)
+    if not isinstance(fused, bool):
+        raise ValueError(
+            f"model.fused_lm_head_loss must be true or false, got {fused!r}"
+        )
     nl = int(model.get("num_layers", 1))
     if pp > 1 and nl < pp:
         raise ValueError(f"num_layers {nl} < PP {pp}")

@@ -37,6 +37,7 @@ sources = [
         "cross_entropy.hip",
         "moe_gemm.hip",
         "lora.hip",
+        "lm_head_loss.hip",
         "probe.hip",
     )
 ]
