@@ -45,8 +45,8 @@ from ..parallel.mappings import (
 from ..ops import flash_attn_func, swiglu
 from ..ops.flash_attn import mask_to_kv_range_tensors, segment_bounds
 from ..ops.flash_decode import flash_attn_decode
-from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
-from ..ops.rmsnorm import RMSNorm
+from ..ops.rope import apply_rotary_pos_emb_pair, build_rope_cache
+from ..ops.rmsnorm import RMSNorm, add_rmsnorm
 
 
 @dataclass
@@ -287,8 +287,7 @@ class LlamaAttention(nn.Module):
         q = q.view(s_full, b, self.n_heads_local, d).permute(1, 2, 0, 3)
         k = k.view(s_full, b, self.n_kv_local, d).permute(1, 2, 0, 3)
         v = v.view(s_full, b, self.n_kv_local, d).permute(1, 2, 0, 3)
-        q = apply_rotary_pos_emb(q, cos, sin, pos_offset)
-        k = apply_rotary_pos_emb(k, cos, sin, pos_offset)
+        q, k = apply_rotary_pos_emb_pair(q, k, cos, sin, pos_offset)
         if pad_mask is not None:
             # padded batch (e.g. left-padded DPO prompts): eager SDPA with
             # the combined causal+padding mask (reference CoreAttention
@@ -411,13 +410,23 @@ class LlamaDecoderLayer(nn.Module):
 
     def forward(self, x, cos, sin, pos_offset: int = 0, cache=None,
                 layer_idx: int = 0, pad_mask=None, kv_range=None,
-                seg_bounds=None):
-        x = x + self.self_attn(self.input_layernorm(x), cos, sin, pos_offset,
-                               cache=cache, layer_idx=layer_idx,
-                               pad_mask=pad_mask, kv_range=kv_range,
-                               seg_bounds=seg_bounds)
-        x = x + self.mlp(self.post_attention_layernorm(x))
-        return x
+                seg_bounds=None, delta=None, carry=False):
+        """The residual stream enters as x (+ delta, when the caller passes
+        the previous block's output unadded) and, with carry=True, leaves as
+        the pair (h, mlp_out) instead of h + mlp_out: each residual add then
+        runs inside the norm that follows it (ops.rmsnorm.add_rmsnorm)."""
+        n1 = self.input_layernorm
+        if delta is None:
+            h = n1(x)
+        else:
+            x, h = add_rmsnorm(x, delta, n1.weight, n1.variance_epsilon)
+        a = self.self_attn(h, cos, sin, pos_offset, cache=cache,
+                           layer_idx=layer_idx, pad_mask=pad_mask,
+                           kv_range=kv_range, seg_bounds=seg_bounds)
+        n2 = self.post_attention_layernorm
+        x, h = add_rmsnorm(x, a, n2.weight, n2.variance_epsilon)
+        m = self.mlp(h)
+        return (x, m) if carry else x + m
 
 
 class LlamaModel(nn.Module):
@@ -555,18 +564,29 @@ class LlamaModel(nn.Module):
         if self.cfg.sequence_parallel:
             x = scatter_to_sequence_parallel_region(x)
         full_ckpt = self.cfg.activation_checkpoint == "full" and self.training
+        # the stream travels as (x, delta): a block's last residual add runs
+        # inside the next block's first norm, the last one inside self.norm
+        delta = None
         for li, layer in enumerate(self.layers):
             if full_ckpt:
-                x = _ckpt(layer, x, self.rope_cos, self.rope_sin, pos_offset,
-                          use_reentrant=False, pad_mask=pad_mask,
-                          kv_range=kv_range, seg_bounds=seg_bounds)
+                x, delta = _ckpt(layer, x, self.rope_cos, self.rope_sin,
+                                 pos_offset, use_reentrant=False,
+                                 pad_mask=pad_mask, kv_range=kv_range,
+                                 seg_bounds=seg_bounds, delta=delta,
+                                 carry=True)
             else:
-                x = layer(x, self.rope_cos, self.rope_sin, pos_offset,
-                          cache=kv_cache, layer_idx=li, pad_mask=pad_mask,
-                          kv_range=kv_range, seg_bounds=seg_bounds)
+                x, delta = layer(x, self.rope_cos, self.rope_sin, pos_offset,
+                                 cache=kv_cache, layer_idx=li,
+                                 pad_mask=pad_mask, kv_range=kv_range,
+                                 seg_bounds=seg_bounds, delta=delta,
+                                 carry=True)
         if kv_cache is not None:
             kv_cache.seq_len += input_ids.size(1)
-        x = self.norm(x)
+        if delta is None:  # no layers
+            x = self.norm(x)
+        else:
+            x = add_rmsnorm(x, delta, self.norm.weight,
+                            self.norm.variance_epsilon)[1]
         if self.cfg.sequence_parallel:
             x = gather_from_sequence_parallel_region(x)
         return x.transpose(0, 1)  # [b, s, h]

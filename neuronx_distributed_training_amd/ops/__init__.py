@@ -11,7 +11,9 @@ Every op has two paths:
   so have no kernel (``bf16_kernels_for``).
 
 Kernel inventory (replacing the reference's NKI/apex device stack, SURVEY.md
-§2.3): rmsnorm fwd/bwd, rope fwd/bwd, swiglu fwd/bwd, flash attention
+§2.3): rmsnorm fwd/bwd (also with the residual add in front of it fused in,
+both ways), rope fwd/bwd (also Q and K in one vectorised launch), swiglu
+fwd/bwd, flash attention
 fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
 sequences, and attention dropout regenerated in-kernel from a counter-based
 keep mask, with a stand-alone mask kernel for tests), split-KV flash decode
@@ -94,6 +96,18 @@ def bf16_kernels_for(t: torch.Tensor):
     if t.is_cuda and t.dtype == torch.bfloat16:
         return require_extension()
     return None
+
+
+def fused_glue() -> bool:
+    """The residual add fused into RMSNorm (ops.rmsnorm.add_rmsnorm) and the
+    one-launch RoPE of Q and K (ops.rope.apply_rotary_pos_emb_pair) are the
+    default; NXDT_FUSED_GLUE=0 (read per call) makes both evaluate the
+    unfused calls they replaced, for A/B. The two are bit-identical except
+    for the RMSNorm weight gradient's cross-block atomic order."""
+    env = os.environ.get("NXDT_FUSED_GLUE", "") or "1"
+    if env not in ("0", "1"):
+        raise ValueError(f"NXDT_FUSED_GLUE must be '0' or '1', got {env!r}")
+    return env == "1"
 
 
 from .rmsnorm import rmsnorm  # noqa: E402

@@ -88,6 +88,63 @@ std::vector<torch::Tensor> rmsnorm_bwd(torch::Tensor dy, torch::Tensor x,
   return {dx, dw32};
 }
 
+// Residual add fused into the norm: {h = x + delta (bf16), y, invrms of h},
+// bit-equal to torch's add followed by rmsnorm_fwd.
+std::vector<torch::Tensor> add_rmsnorm_fwd(torch::Tensor x,
+                                           torch::Tensor delta,
+                                           torch::Tensor w, double eps) {
+  check_dense(x, x, torch::kBFloat16, "add_rmsnorm_fwd", "x");
+  TORCH_CHECK(x.dim() == 2, "add_rmsnorm_fwd: x must be [N, H]");
+  auto N = x.size(0);
+  auto H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  check_dense(delta, x, torch::kBFloat16, "add_rmsnorm_fwd", "delta");
+  TORCH_CHECK(delta.sizes() == x.sizes(),
+              "add_rmsnorm_fwd: delta must have x's shape");
+  check_vec(w, x, torch::kBFloat16, H, "add_rmsnorm_fwd", "w");
+  auto h = torch::empty_like(x);
+  auto y = torch::empty_like(x);
+  auto invrms = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  if (N == 0 || H == 0) return {h, y, invrms};
+  launch_add_rmsnorm_fwd(x.data_ptr(), delta.data_ptr(), w.data_ptr(),
+                         h.data_ptr(), y.data_ptr(), invrms.data_ptr(), N,
+                         (int)H, (float)eps, cur_stream());
+  return {h, y, invrms};
+}
+
+// {dx bf16 [N, H], dw fp32 [H]} of the fused op: dx = dh + (the dx of
+// rmsnorm_bwd at h), summed in bf16 as autograd sums the two gradients of the
+// residual tensor; without dh, rmsnorm_bwd's dx itself.
+std::vector<torch::Tensor> add_rmsnorm_bwd(torch::Tensor dy,
+                                           c10::optional<torch::Tensor> dh,
+                                           torch::Tensor h, torch::Tensor w,
+                                           torch::Tensor invrms) {
+  check_dense(h, h, torch::kBFloat16, "add_rmsnorm_bwd", "h");
+  TORCH_CHECK(h.dim() == 2, "add_rmsnorm_bwd: h must be [N, H]");
+  auto N = h.size(0);
+  auto H = h.size(1);
+  TORCH_CHECK(H % 8 == 0, "hidden must be divisible by 8");
+  check_dense(dy, h, torch::kBFloat16, "add_rmsnorm_bwd", "dy");
+  TORCH_CHECK(dy.sizes() == h.sizes(),
+              "add_rmsnorm_bwd: dy must have h's shape");
+  if (dh.has_value()) {
+    check_dense(*dh, h, torch::kBFloat16, "add_rmsnorm_bwd", "dh");
+    TORCH_CHECK(dh->sizes() == h.sizes(),
+                "add_rmsnorm_bwd: dh must have h's shape");
+  }
+  check_vec(w, h, torch::kBFloat16, H, "add_rmsnorm_bwd", "w");
+  check_vec(invrms, h, torch::kFloat32, N, "add_rmsnorm_bwd", "invrms");
+  auto dx = torch::empty_like(h);
+  auto dw32 = torch::zeros({H}, h.options().dtype(torch::kFloat32));
+  if (N == 0 || H == 0) return {dx, dw32};
+  launch_add_rmsnorm_bwd(dy.data_ptr(),
+                         dh.has_value() ? dh->data_ptr() : nullptr,
+                         h.data_ptr(), w.data_ptr(), invrms.data_ptr(),
+                         dx.data_ptr(), dw32.data_ptr(), N, (int)H,
+                         cur_stream());
+  return {dx, dw32};
+}
+
 torch::Tensor swiglu_fwd(torch::Tensor gu) {
   CHECK_IN(gu);
   check_dense(gu, gu, torch::kBFloat16, "swiglu_fwd", "gate_up");
@@ -121,18 +178,18 @@ torch::Tensor swiglu_bwd(torch::Tensor dy, torch::Tensor gu) {
   return dgu;
 }
 
-torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
-                       long pos_offset, long pos_offset2) {
-  // x: logical [b, h, s, d], any strides with d contiguous (e.g. a view of
-  // the fused QKV output). Returns a [s, b, h, d]-contiguous tensor exposed
-  // as a [b, h, s, d] view — zero permute copies in the attention path.
-  // pos_offset2 >= 0: zigzag CP layout — rows [s/2, s) take positions
-  // pos_offset2 + i instead of pos_offset + s/2 + i.
+// Argument contract of the RoPE bindings for one tensor x: logical
+// [b, h, s, d] bf16 on the GPU, any strides with d contiguous (e.g. a view of
+// the fused QKV output), and fp32 tables that reach every position read.
+// pos_offset2 >= 0: zigzag CP layout — rows [s/2, s) take positions
+// pos_offset2 + i instead of pos_offset + s/2 + i.
+static void check_rope(const torch::Tensor& x, const torch::Tensor& cost,
+                       const torch::Tensor& sint, long pos_offset,
+                       long pos_offset2) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 && x.stride(3) == 1,
               "rope: x must be [b, h, s, d] on GPU with d contiguous");
   TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "rope: x must be bf16");
-  int B = (int)x.size(0), H = (int)x.size(1), S = (int)x.size(2),
-      D = (int)x.size(3);
+  int S = (int)x.size(2), D = (int)x.size(3);
   // the kernel pairs column d with d + D / 2
   TORCH_CHECK(D % 2 == 0, "rope: head_dim must be even, got ", D);
   TORCH_CHECK(pos_offset2 < 0 || S % 2 == 0, "zigzag rope needs even s");
@@ -155,6 +212,15 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
     TORCH_CHECK(S == 0 || t->size(0) >= need, "rope: ", name, " table has ",
                 t->size(0), " rows, positions reach ", need);
   }
+}
+
+torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
+                       long pos_offset, long pos_offset2) {
+  // Returns a [s, b, h, d]-contiguous tensor exposed as a [b, h, s, d] view
+  // — zero permute copies in the attention path.
+  check_rope(x, cost, sint, pos_offset, pos_offset2);
+  int B = (int)x.size(0), H = (int)x.size(1), S = (int)x.size(2),
+      D = (int)x.size(3);
   auto cos_c = cost.contiguous();
   auto sin_c = sint.contiguous();
   auto y_mem = torch::empty({S, B, H, D}, x.options());
@@ -164,6 +230,37 @@ torch::Tensor rope_fwd(torch::Tensor x, torch::Tensor cost, torch::Tensor sint,
                   y_mem.data_ptr(), S, B, H, D, xstr, (int)pos_offset,
                   (int)pos_offset2, 1.0f, cur_stream());
   return y_mem.permute({1, 2, 0, 3});
+}
+
+// q [b, hq, s, d] and k [b, hkv, s, d] of one attention call through one
+// launch; each is held to rope_fwd's contract and the result is bit-equal to
+// rope_fwd on each. sin_sign multiplies the sin table in the kernel: the
+// backward passes -1 instead of a negated copy of the table.
+std::vector<torch::Tensor> rope_fwd_pair(torch::Tensor q, torch::Tensor k,
+                                         torch::Tensor cost,
+                                         torch::Tensor sint, long pos_offset,
+                                         long pos_offset2, double sin_sign) {
+  check_rope(q, cost, sint, pos_offset, pos_offset2);
+  check_rope(k, cost, sint, pos_offset, pos_offset2);
+  TORCH_CHECK(k.device() == q.device(), "rope: k must be on q's GPU");
+  TORCH_CHECK(k.size(0) == q.size(0) && k.size(2) == q.size(2) &&
+                  k.size(3) == q.size(3),
+              "rope: q and k must agree in b, s and d");
+  int B = (int)q.size(0), HQ = (int)q.size(1), S = (int)q.size(2),
+      D = (int)q.size(3), HKV = (int)k.size(1);
+  auto cos_c = cost.contiguous();
+  auto sin_c = sint.contiguous();
+  auto yq = torch::empty({S, B, HQ, D}, q.options());
+  auto yk = torch::empty({S, B, HKV, D}, k.options());
+  if (yq.numel() + yk.numel() > 0) {
+    long qstr[3] = {q.stride(2), q.stride(0), q.stride(1)};  // s, b, h
+    long kstr[3] = {k.stride(2), k.stride(0), k.stride(1)};
+    launch_rope_fwd_pair(q.data_ptr(), k.data_ptr(), cos_c.data_ptr(),
+                         sin_c.data_ptr(), yq.data_ptr(), yk.data_ptr(), S, B,
+                         HQ, HKV, D, qstr, kstr, (int)pos_offset,
+                         (int)pos_offset2, (float)sin_sign, cur_stream());
+  }
+  return {yq.permute({1, 2, 0, 3}), yk.permute({1, 2, 0, 3})};
 }
 
 static void check_adamw_f32(const torch::Tensor& t, const torch::Tensor& p,
@@ -1019,6 +1116,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_fwd", &rope_fwd, py::arg("x"), py::arg("cost"), py::arg("sint"),
         py::arg("pos_offset"), py::arg("pos_offset2") = -1);
+  m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd, py::arg("x"), py::arg("delta"),
+        py::arg("w"), py::arg("eps"));
+  m.def("add_rmsnorm_bwd", &add_rmsnorm_bwd, py::arg("dy"), py::arg("dh"),
+        py::arg("h"), py::arg("w"), py::arg("invrms"));
+  m.def("rope_fwd_pair", &rope_fwd_pair, py::arg("q"), py::arg("k"),
+        py::arg("cost"), py::arg("sint"), py::arg("pos_offset"),
+        py::arg("pos_offset2") = -1, py::arg("sin_sign") = 1.0);
   m.def("adamw_step", &adamw_step, py::arg("p"), py::arg("g"), py::arg("m"),
         py::arg("v"), py::arg("wd_mask"), py::arg("lr"), py::arg("b1"),
         py::arg("b2"), py::arg("eps"), py::arg("wd"), py::arg("step"),

@@ -175,6 +175,16 @@ void launch_rmsnorm_fwd(const void* x, const void* w, void* y, void* invrms,
 void launch_rmsnorm_bwd(const void* dy, const void* x, const void* w,
                         const void* invrms, void* dx, void* dw, long N, int H,
                         hipStream_t stream);
+// rmsnorm.hip, fused residual add: h = bf16(x + delta), y / invrms = the
+// norm of h; dx = bf16(dh + dxn) with dxn what launch_rmsnorm_bwd stores,
+// dh may be null (dx = dxn). All outputs but dw bit-equal to the unfused
+// calls; dw fp32 [H], zeroed by the caller.
+void launch_add_rmsnorm_fwd(const void* x, const void* delta, const void* w,
+                            void* h, void* y, void* invrms, long N, int H,
+                            float eps, hipStream_t stream);
+void launch_add_rmsnorm_bwd(const void* dy, const void* dh, const void* h,
+                            const void* w, const void* invrms, void* dx,
+                            void* dw, long N, int H, hipStream_t stream);
 void launch_swiglu_fwd(const void* gu, void* y, long N, int I,
                        hipStream_t stream);
 void launch_swiglu_bwd(const void* dy, const void* gu, void* dgu, long N,
@@ -183,6 +193,16 @@ void launch_rope_fwd(const void* x, const void* cost, const void* sint,
                      void* y, int S, int B, int H, int D, const long* xstr,
                      int pos_offset, int pos_offset2, float sin_sign,
                      hipStream_t stream);
+// rope.hip: q [b, hq, s, d] and k [b, hkv, s, d] in one launch, each with
+// its own (seq, batch, head) strides; yq / yk dense [s, b, h, d]. Bit-equal
+// to launch_rope_fwd on each tensor. 16-byte accesses where D % 16 == 0,
+// the bases are 16 B-aligned and the strides multiples of 8; otherwise the
+// scalar kernel of launch_rope_fwd, once per tensor.
+void launch_rope_fwd_pair(const void* q, const void* k, const void* cost,
+                          const void* sint, void* yq, void* yk, int S, int B,
+                          int HQ, int HKV, int D, const long* qstr,
+                          const long* kstr, int pos_offset, int pos_offset2,
+                          float sin_sign, hipStream_t stream);
 void launch_adamw(void* p, const void* g, void* m, void* v,
                   const void* wd_mask, const void* grad_scale, void* p_bf16,
                   long n, float lr, float beta1, float beta2, float eps,

@@ -69,6 +69,52 @@ def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float = 1e-5) -> torch.T
     return _RMSNormFn.apply(x, weight, eps)
 
 
+class _AddRMSNormFn(torch.autograd.Function):
+    """(x, delta) -> (h = x + delta, y = rmsnorm(h)) in one kernel each way,
+    bf16 on GPU only. h's gradient (absent when nothing else consumes h) is
+    summed into the norm's dx inside the backward kernel."""
+
+    @staticmethod
+    def forward(ctx, x, delta, weight, eps):
+        k = bf16_kernels_for(x)
+        shp = x.shape
+        x2 = x.reshape(-1, shp[-1]).contiguous()
+        d2 = delta.reshape(-1, shp[-1]).contiguous()
+        h, y, invrms = k.add_rmsnorm_fwd(x2, d2, _kernel_weight(weight, x2), eps)
+        ctx.save_for_backward(h, weight, invrms)
+        ctx.set_materialize_grads(False)
+        return h.view(shp), y.view(shp)
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        h, weight, invrms = ctx.saved_tensors
+        if dy is None:  # only h was used: the add's own backward
+            return dh, dh, None, None
+        k = bf16_kernels_for(dy)
+        dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
+        dh2 = None if dh is None else dh.reshape(-1, dh.shape[-1]).contiguous()
+        dx, dw = k.add_rmsnorm_bwd(dy2, dh2, h, _kernel_weight(weight, h),
+                                   invrms)
+        dx = dx.view(dy.shape)
+        return dx, dx, dw.to(weight.dtype), None
+
+
+def add_rmsnorm(x: torch.Tensor, delta: torch.Tensor, weight: torch.Tensor,
+                eps: float = 1e-5):
+    """The residual add in front of a norm, fused into it: returns
+    (h, y) = (x + delta, rmsnorm(x + delta)). bf16 GPU tensors take the fused
+    kernels, whose results are bit-equal to the two ops (the weight gradient
+    up to its atomic order); everything else, and NXDT_FUSED_GLUE=0, is the
+    two ops themselves."""
+    from . import fused_glue
+
+    if (fused_glue() and x.dtype == delta.dtype and x.shape == delta.shape
+            and delta.is_cuda and bf16_kernels_for(x) is not None):
+        return _AddRMSNormFn.apply(x, delta, weight, eps)
+    h = x + delta
+    return h, rmsnorm(h, weight, eps)
+
+
 class RMSNorm(torch.nn.Module):
     def __init__(self, hidden_size: int, eps: float = 1e-5, dtype: torch.dtype = torch.float32):
         super().__init__()

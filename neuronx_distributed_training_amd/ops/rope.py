@@ -93,6 +93,53 @@ class _RopeFn(torch.autograd.Function):
         return dx, None, None, None, None
 
 
+class _RopePairFn(torch.autograd.Function):
+    """Q and K of one attention call through one launch each way (bf16 on
+    GPU only); the backward is the same kernel with sin_sign = -1, no
+    negated copy of the table."""
+
+    @staticmethod
+    def forward(ctx, q, k, cos, sin, pos_offset: int, pos_offset2: int):
+        ctx.save_for_backward(cos, sin)
+        ctx.pos_offset = pos_offset
+        ctx.pos_offset2 = pos_offset2
+        ext = bf16_kernels_for(q)
+        return tuple(ext.rope_fwd_pair(q, k, cos, sin, pos_offset,
+                                       pos_offset2, 1.0))
+
+    @staticmethod
+    def backward(ctx, dq, dk):
+        cos, sin = ctx.saved_tensors
+        ext = bf16_kernels_for(dq)
+        dq, dk = (t if t.stride(-1) == 1 else t.contiguous() for t in (dq, dk))
+        dxq, dxk = ext.rope_fwd_pair(dq, dk, cos, sin, ctx.pos_offset,
+                                     ctx.pos_offset2, -1.0)
+        return dxq, dxk, None, None, None, None
+
+
+def _offsets(pos_offset):
+    if isinstance(pos_offset, (tuple, list)):
+        return int(pos_offset[0]), int(pos_offset[1])
+    return int(pos_offset), -1
+
+
+def apply_rotary_pos_emb_pair(
+    q: torch.Tensor, k: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor,
+    pos_offset=0,
+):
+    """apply_rotary_pos_emb on q [b, hq, s, d] and k [b, hkv, s, d] of one
+    attention call. bf16 GPU tensors take one launch for both, bit-equal to
+    the two calls; everything else, and NXDT_FUSED_GLUE=0, is the two calls."""
+    from . import fused_glue
+
+    if (fused_glue() and q.dtype == k.dtype and k.is_cuda
+            and bf16_kernels_for(q) is not None):
+        off, off2 = _offsets(pos_offset)
+        return _RopePairFn.apply(q, k, cos, sin, off, off2)
+    return (apply_rotary_pos_emb(q, cos, sin, pos_offset),
+            apply_rotary_pos_emb(k, cos, sin, pos_offset))
+
+
 def apply_rotary_pos_emb(
     x: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos_offset=0
 ) -> torch.Tensor:
