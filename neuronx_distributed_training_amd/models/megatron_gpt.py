@@ -34,8 +34,9 @@ from ..parallel.mappings import (
     scatter_to_sequence_parallel_region,
 )
 from ..modules.moe import ExpertMLPs, MoE, RouterSinkhorn, RouterTopK, load_balancing_loss_func
-from ..ops import flash_attn_func, swiglu
+from ..ops import flash_attn_func, geglu, gelu, gpt_glue, swiglu
 from ..ops.flash_attn import draw_dropout_rng
+from ..ops.layernorm import LayerNorm
 from ..ops.rmsnorm import RMSNorm
 from ..ops.rope import apply_rotary_pos_emb, build_rope_cache
 
@@ -109,7 +110,7 @@ def _init(std):
 def make_norm(cfg: GPTConfig):
     if cfg.normalization == "rmsnorm":
         return RMSNorm(cfg.hidden_size, cfg.layernorm_epsilon, dtype=cfg.torch_dtype)
-    return nn.LayerNorm(cfg.hidden_size, cfg.layernorm_epsilon, dtype=cfg.torch_dtype)
+    return LayerNorm(cfg.hidden_size, cfg.layernorm_epsilon, dtype=cfg.torch_dtype)
 
 
 class ParallelMLP(nn.Module):
@@ -135,11 +136,16 @@ class ParallelMLP(nn.Module):
         h = self.dense_h_to_4h(x)
         if self.activation == "swiglu":
             h = swiglu(h)
+        elif not gpt_glue():  # NXDT_GPT_GLUE=0: the torch calls, for A/B
+            if self.activation == "geglu":
+                g, u = h.chunk(2, dim=-1)
+                h = F.gelu(g) * u
+            else:
+                h = F.gelu(h)
         elif self.activation == "geglu":
-            g, u = h.chunk(2, dim=-1)
-            h = F.gelu(g) * u
+            h = geglu(h)
         else:
-            h = F.gelu(h)
+            h = gelu(h)
         return self.dense_4h_to_h(h)
 
 

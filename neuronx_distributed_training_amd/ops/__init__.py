@@ -7,13 +7,15 @@ Every op has two paths:
   device; if the extension is missing while such a tensor is on GPU the op
   raises instead of silently falling back;
 - a plain PyTorch fp32 reference path used on CPU (unit tests, gloo runs)
-  and, for RMSNorm / SwiGLU / RoPE, for GPU tensors that are not bf16 and
-  so have no kernel (``bf16_kernels_for``).
+  and, for RMSNorm / SwiGLU / RoPE / LayerNorm / GELU / GEGLU, for GPU
+  tensors that are not bf16 and so have no kernel (``bf16_kernels_for``).
 
 Kernel inventory (replacing the reference's NKI/apex device stack, SURVEY.md
 §2.3): rmsnorm fwd/bwd (also with the residual add in front of it fused in,
 both ways), rope fwd/bwd (also Q and K in one vectorised launch), swiglu
-fwd/bwd, flash attention
+fwd/bwd, layernorm fwd/bwd (wave per row up to H = 2048, block per row
+beyond; two-stage atomic-free dw / db), exact gelu and geglu fwd/bwd (the
+Megatron GPT family's glue, NXDT_GPT_GLUE), flash attention
 fwd/bwd (causal, GQA, bf16, MFMA+LDS online softmax; padded batches, packed
 sequences, and attention dropout regenerated in-kernel from a counter-based
 keep mask, with a stand-alone mask kernel for tests), split-KV flash decode
@@ -89,8 +91,8 @@ def kernels_for(t: torch.Tensor):
 
 
 def bf16_kernels_for(t: torch.Tensor):
-    """The extension for a bf16 GPU tensor: the RMSNorm, SwiGLU and RoPE
-    kernels read bf16 and nothing else. None for CPU tensors and for GPU
+    """The extension for a bf16 GPU tensor: the RMSNorm, SwiGLU, RoPE,
+    LayerNorm and GELU / GEGLU kernels read bf16 and nothing else. None for CPU tensors and for GPU
     tensors of any other dtype (fp32 / fp16 / fp64 modules), which have no
     kernel and take the plain torch formulas on their own device."""
     if t.is_cuda and t.dtype == torch.bfloat16:
@@ -110,7 +112,22 @@ def fused_glue() -> bool:
     return env == "1"
 
 
+def gpt_glue() -> bool:
+    """The Megatron GPT family's LayerNorm module and MLP activation
+    (ops.layernorm.LayerNorm, and gelu / geglu in ParallelMLP) run the HIP
+    kernels by default; NXDT_GPT_GLUE=0 (read per call) makes them evaluate
+    the torch calls they replaced (nn.LayerNorm.forward, F.gelu), for A/B.
+    The functions ops.layernorm, ops.gelu and ops.geglu themselves always
+    take the kernels for bf16 GPU tensors."""
+    env = os.environ.get("NXDT_GPT_GLUE", "") or "1"
+    if env not in ("0", "1"):
+        raise ValueError(f"NXDT_GPT_GLUE must be '0' or '1', got {env!r}")
+    return env == "1"
+
+
 from .rmsnorm import rmsnorm  # noqa: E402
+from .layernorm import layernorm  # noqa: E402
+from .gelu import geglu, gelu  # noqa: E402
 from .rope import apply_rotary_pos_emb  # noqa: E402
 from .swiglu import swiglu  # noqa: E402
 from .flash_attn import (  # noqa: E402
@@ -132,6 +149,9 @@ __all__ = [
     "rmsnorm",
     "apply_rotary_pos_emb",
     "swiglu",
+    "layernorm",
+    "gelu",
+    "geglu",
     "flash_attn_func",
     "flash_attn_decode",
     "lora_delta_add",

@@ -1107,6 +1107,112 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor targets,
   return dl;
 }
 
+// ---- LayerNorm and GELU / GEGLU (layernorm.hip, gelu.hip) ----
+
+// {y bf16 [N, H], mean fp32 [N], rstd fp32 [N]}
+std::vector<torch::Tensor> layernorm_fwd(torch::Tensor x, torch::Tensor w,
+                                         torch::Tensor b, double eps) {
+  check_dense(x, x, torch::kBFloat16, "layernorm_fwd", "x");
+  TORCH_CHECK(x.dim() == 2, "layernorm_fwd: x must be [N, H]");
+  const long N = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "layernorm_fwd: hidden must be divisible by 8");
+  TORCH_CHECK(N < (1L << 31) && H < (1L << 30), "layernorm_fwd: too large");
+  check_vec(w, x, torch::kBFloat16, H, "layernorm_fwd", "w");
+  check_vec(b, x, torch::kBFloat16, H, "layernorm_fwd", "b");
+  auto y = torch::empty_like(x);
+  auto mean = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  auto rstd = torch::empty({N}, x.options().dtype(torch::kFloat32));
+  if (N == 0 || H == 0) return {y, mean, rstd};
+  launch_layernorm_fwd(x.data_ptr(), w.data_ptr(), b.data_ptr(), y.data_ptr(),
+                       mean.data_ptr(), rstd.data_ptr(), N, (int)H, (float)eps,
+                       cu_count(x), cur_stream());
+  return {y, mean, rstd};
+}
+
+// {dx bf16 [N, H], dw fp32 [H], db fp32 [H]}: the kernels' fp32 sums
+// themselves; the caller casts them to the dtypes of its parameters.
+std::vector<torch::Tensor> layernorm_bwd(torch::Tensor dy, torch::Tensor x,
+                                         torch::Tensor w, torch::Tensor mean,
+                                         torch::Tensor rstd) {
+  check_dense(x, x, torch::kBFloat16, "layernorm_bwd", "x");
+  TORCH_CHECK(x.dim() == 2, "layernorm_bwd: x must be [N, H]");
+  const long N = x.size(0), H = x.size(1);
+  TORCH_CHECK(H % 8 == 0, "layernorm_bwd: hidden must be divisible by 8");
+  TORCH_CHECK(N < (1L << 31) && H < (1L << 30), "layernorm_bwd: too large");
+  check_dense(dy, x, torch::kBFloat16, "layernorm_bwd", "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "layernorm_bwd: dy must have x's shape");
+  check_vec(w, x, torch::kBFloat16, H, "layernorm_bwd", "w");
+  check_vec(mean, x, torch::kFloat32, N, "layernorm_bwd", "mean");
+  check_vec(rstd, x, torch::kFloat32, N, "layernorm_bwd", "rstd");
+  auto dx = torch::empty_like(x);
+  const auto f32 = x.options().dtype(torch::kFloat32);
+  if (N == 0 || H == 0) {
+    auto z = torch::zeros({2, H}, f32);
+    return {dx, z[0], z[1]};
+  }
+  const int grid = layernorm_bwd_grid(N, (int)H, cu_count(x));
+  auto part = torch::empty({grid, 2, H}, f32);
+  auto dwdb = torch::empty({2, H}, f32);
+  launch_layernorm_bwd(dy.data_ptr(), x.data_ptr(), w.data_ptr(),
+                       mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
+                       part.data_ptr(), dwdb.data_ptr(), N, (int)H, grid,
+                       cur_stream());
+  return {dx, dwdb[0], dwdb[1]};
+}
+
+torch::Tensor gelu_fwd(torch::Tensor x) {
+  check_dense(x, x, torch::kBFloat16, "gelu_fwd", "x");
+  TORCH_CHECK(x.dim() == 2, "gelu_fwd: x must be [N, I]");
+  TORCH_CHECK(x.size(1) % 8 == 0, "gelu_fwd: I must be divisible by 8");
+  auto y = torch::empty_like(x);
+  if (x.numel() == 0) return y;
+  launch_gelu_fwd(x.data_ptr(), y.data_ptr(), x.numel(), cur_stream());
+  return y;
+}
+
+torch::Tensor gelu_bwd(torch::Tensor dy, torch::Tensor x) {
+  check_dense(x, x, torch::kBFloat16, "gelu_bwd", "x");
+  TORCH_CHECK(x.dim() == 2, "gelu_bwd: x must be [N, I]");
+  TORCH_CHECK(x.size(1) % 8 == 0, "gelu_bwd: I must be divisible by 8");
+  check_dense(dy, x, torch::kBFloat16, "gelu_bwd", "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes(), "gelu_bwd: dy must have x's shape");
+  auto dx = torch::empty_like(x);
+  if (x.numel() == 0) return dx;
+  launch_gelu_bwd(dy.data_ptr(), x.data_ptr(), dx.data_ptr(), x.numel(),
+                  cur_stream());
+  return dx;
+}
+
+torch::Tensor geglu_fwd(torch::Tensor gu) {
+  check_dense(gu, gu, torch::kBFloat16, "geglu_fwd", "gate_up");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) % 2 == 0,
+              "geglu_fwd: gate_up must be [N, 2 * I]");
+  const long N = gu.size(0), I = gu.size(1) / 2;
+  TORCH_CHECK(I % 8 == 0, "geglu_fwd: I must be divisible by 8");
+  TORCH_CHECK(I < (1L << 30), "geglu_fwd: too large");
+  auto y = torch::empty({N, I}, gu.options());
+  if (N == 0 || I == 0) return y;
+  launch_geglu_fwd(gu.data_ptr(), y.data_ptr(), N, (int)I, cur_stream());
+  return y;
+}
+
+torch::Tensor geglu_bwd(torch::Tensor dy, torch::Tensor gu) {
+  check_dense(gu, gu, torch::kBFloat16, "geglu_bwd", "gate_up");
+  TORCH_CHECK(gu.dim() == 2 && gu.size(1) % 2 == 0,
+              "geglu_bwd: gate_up must be [N, 2 * I]");
+  const long N = gu.size(0), I = gu.size(1) / 2;
+  TORCH_CHECK(I % 8 == 0, "geglu_bwd: I must be divisible by 8");
+  TORCH_CHECK(I < (1L << 30), "geglu_bwd: too large");
+  check_dense(dy, gu, torch::kBFloat16, "geglu_bwd", "dy");
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) == N && dy.size(1) == I,
+              "geglu_bwd: dy must be [N, I]");
+  auto dgu = torch::empty_like(gu);
+  if (N == 0 || I == 0) return dgu;
+  launch_geglu_bwd(dy.data_ptr(), gu.data_ptr(), dgu.data_ptr(), N, (int)I,
+                   cur_stream());
+  return dgu;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1114,6 +1220,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rmsnorm_bwd", &rmsnorm_bwd);
   m.def("swiglu_fwd", &swiglu_fwd);
   m.def("swiglu_bwd", &swiglu_bwd);
+  m.def("layernorm_fwd", &layernorm_fwd, py::arg("x"), py::arg("w"),
+        py::arg("b"), py::arg("eps"));
+  m.def("layernorm_bwd", &layernorm_bwd, py::arg("dy"), py::arg("x"),
+        py::arg("w"), py::arg("mean"), py::arg("rstd"));
+  m.def("gelu_fwd", &gelu_fwd, py::arg("x"));
+  m.def("gelu_bwd", &gelu_bwd, py::arg("dy"), py::arg("x"));
+  m.def("geglu_fwd", &geglu_fwd, py::arg("gate_up"));
+  m.def("geglu_bwd", &geglu_bwd, py::arg("dy"), py::arg("gate_up"));
   m.def("rope_fwd", &rope_fwd, py::arg("x"), py::arg("cost"), py::arg("sint"),
         py::arg("pos_offset"), py::arg("pos_offset2") = -1);
   m.def("add_rmsnorm_fwd", &add_rmsnorm_fwd, py::arg("x"), py::arg("delta"),

@@ -108,6 +108,41 @@ constexpr int lmhead_vtiles(long V) { return (int)lmhead_tiles(V, LMHEAD_BN); }
 static_assert(lmhead_vtiles(128) == 1 && lmhead_vtiles(136) == 2,
               "one 8-column group past a tile is a tile of its own");
 
+// ---- LayerNorm (layernorm.hip) ----
+
+// How a row of H elements (H % 8 == 0) is held. LN_WAVE: H <= 2048, one
+// 64-lane wave per row, layernorm_vecs(H) 16-byte vectors per lane.
+// LN_BLOCK: H <= 8192, a 256-thread block per row, that many vectors per
+// thread. LN_LOOPED: longer rows, read twice (layernorm_vecs == 0).
+enum LayerNormForm { LN_WAVE, LN_BLOCK, LN_LOOPED };
+constexpr LayerNormForm layernorm_form(int H) {
+  return H <= 2048 ? LN_WAVE : H <= 8192 ? LN_BLOCK : LN_LOOPED;
+}
+constexpr int layernorm_vecs(int H) {
+  const int nvec = H >> 3;
+  return nvec <= 64 ? 1 : nvec <= 128 ? 2 : nvec <= 256 ? 4
+         : nvec <= 512 ? 2 : nvec <= 1024 ? 4 : 0;
+}
+static_assert(layernorm_form(2048) == LN_WAVE && layernorm_vecs(2048) == 4 &&
+                  layernorm_vecs(1032) == 4 && layernorm_vecs(8) == 1,
+              "wave form: up to 4 vectors a lane, 3 rounded up");
+static_assert(layernorm_form(2056) == LN_BLOCK && layernorm_vecs(2056) == 2 &&
+                  layernorm_vecs(8192) == 4 && layernorm_vecs(8200) == 0,
+              "block form up to 8192, looped beyond");
+// Blocks of the backward, each of which writes one fp32 partial [2, H] of
+// (dw, db): two per CU, fewer when the rows run out (a wave-form block takes
+// 4 rows at a time).
+constexpr int layernorm_bwd_grid(long N, int H, int num_cu) {
+  const long want = layernorm_form(H) == LN_WAVE ? (N + 3) / 4 : N;
+  const long cap = 2L * num_cu;
+  return (int)(want < cap ? want : cap);
+}
+static_assert(layernorm_bwd_grid(3, 1032, 256) == 1 &&
+                  layernorm_bwd_grid(1500, 256, 256) == 375 &&
+                  layernorm_bwd_grid(16384, 2048, 256) == 512 &&
+                  layernorm_bwd_grid(9, 4096, 256) == 9,
+              "rows bound the grid before the CUs do");
+
 extern "C" {
 // lm_head_loss.hip: hidden [N, H] and weight [V, H] dense bf16, H % LMHEAD_BK
 // == 0, V % 8 == 0; targets int64 global ids; the shard owns ids
@@ -185,10 +220,30 @@ void launch_add_rmsnorm_fwd(const void* x, const void* delta, const void* w,
 void launch_add_rmsnorm_bwd(const void* dy, const void* dh, const void* h,
                             const void* w, const void* invrms, void* dx,
                             void* dw, long N, int H, hipStream_t stream);
+// layernorm.hip: x, dy [N, H] bf16 dense, w, b [H] bf16, mean / rstd [N]
+// fp32. bwd: part is fp32 scratch [grid, 2, H] with grid =
+// layernorm_bwd_grid(N, H, CUs), every element of which the kernel writes;
+// dwdb [2, H] fp32 = (dw, db), written, not accumulated.
+void launch_layernorm_fwd(const void* x, const void* w, const void* b, void* y,
+                          void* mean, void* rstd, long N, int H, float eps,
+                          int num_cu, hipStream_t stream);
+void launch_layernorm_bwd(const void* dy, const void* x, const void* w,
+                          const void* mean, const void* rstd, void* dx,
+                          void* part, void* dwdb, long N, int H, int grid,
+                          hipStream_t stream);
 void launch_swiglu_fwd(const void* gu, void* y, long N, int I,
                        hipStream_t stream);
 void launch_swiglu_bwd(const void* dy, const void* gu, void* dgu, long N,
                        int I, hipStream_t stream);
+// gelu.hip: exact (erf) GELU over n = N * I bf16 elements (n % 8 == 0), and
+// GEGLU over gate_up [N, 2I] = [gate | up] -> y [N, I], dgu [N, 2I]
+void launch_gelu_fwd(const void* x, void* y, long n, hipStream_t stream);
+void launch_gelu_bwd(const void* dy, const void* x, void* dx, long n,
+                     hipStream_t stream);
+void launch_geglu_fwd(const void* gu, void* y, long N, int I,
+                      hipStream_t stream);
+void launch_geglu_bwd(const void* dy, const void* gu, void* dgu, long N,
+                      int I, hipStream_t stream);
 void launch_rope_fwd(const void* x, const void* cost, const void* sint,
                      void* y, int S, int B, int H, int D, const long* xstr,
                      int pos_offset, int pos_offset2, float sin_sign,

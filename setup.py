@@ -23,6 +23,8 @@ sources = [
         "bindings.cpp",
         "rmsnorm.hip",
         "swiglu.hip",
+        "layernorm.hip",
+        "gelu.hip",
         "rope.hip",
         "adamw.hip",
         "flash_attn_fwd.hip",
