@@ -258,6 +258,24 @@ class ExpertMLPs(nn.Module):
         self.gate_up.expert_model_parallel = True
         self.down.expert_model_parallel = True
 
+    def grouped_chosen(self, x: torch.Tensor, rows: int):
+        """Whether `rows` expert-sorted rows with x's dtype, device and width
+        go to the grouped HIP kernel (truthy) or to the library path: the
+        kernel must take the operands, and NXDT_MOE_GROUPED=1/0 forces;
+        unforced, grouped runs up to 1024 rows per local expert."""
+        from ..ops.moe_gemm import grouped_path_supported
+
+        force = os.environ.get("NXDT_MOE_GROUPED", "")
+        return (
+            rows * x.size(-1)
+            and grouped_path_supported(x, self.gate_up, self.down)
+            and (
+                force == "1"
+                or (force != "0"
+                    and rows <= 1024 * self.num_local)
+            )
+        )
+
     def forward(self, x: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
         """x: [T, H] tokens sorted by local expert; counts: [E_local] token
         counts per local expert. Returns same-order outputs.
@@ -270,19 +288,9 @@ class ExpertMLPs(nn.Module):
         where hipBLASLt's per-GEMM throughput wins — so the grouped path
         runs below GROUPED_MAX_TOKENS_PER_EXPERT and the library path
         (bmm / per-expert loop) above. NXDT_MOE_GROUPED=1/0 forces."""
-        from ..ops.moe_gemm import grouped_expert_mlp, grouped_path_supported
+        from ..ops.moe_gemm import grouped_expert_mlp
 
-        force = os.environ.get("NXDT_MOE_GROUPED", "")
-        use_grouped = (
-            x.numel()
-            and grouped_path_supported(x, self.gate_up, self.down)
-            and (
-                force == "1"
-                or (force != "0"
-                    and x.size(0) <= 1024 * self.num_local)
-            )
-        )
-        if use_grouped:
+        if self.grouped_chosen(x, x.size(0)):
             return grouped_expert_mlp(x, counts, self.gate_up, self.down)
         cl = counts.tolist()
         total = int(sum(cl))
@@ -328,6 +336,18 @@ class MoE(nn.Module):
     Dropless by default; with ``capacity_factor`` set, tokens beyond
     capacity per expert are dropped (their MoE output is 0 — residual
     carries them, matching capacity-factor semantics).
+
+    NXDT_MOE_FUSED=1 (read per call, default 0; any other value raises a
+    ValueError) replaces the chain of torch index ops between the router and
+    the output with the HIP token path of ops.moe_dispatch (plan, permute,
+    grouped expert MLP in the padded layout, fp32 combine), in dropless and
+    capacity mode alike. It applies with EP = 1, at most 64 experts and
+    top-8, where ExpertMLPs would choose the grouped kernel for the T * k
+    rows (in capacity mode the eager path asks that of the kept rows, this
+    one of all T * k: the kept count lives on the device); everywhere else,
+    CPU included, the layer runs the eager code unchanged. The same pairs are
+    kept and the same experts applied; the combine and its backward round
+    once in fp32 where eager rounds per pair in bf16.
     """
 
     def __init__(self, router: RouterTopK, experts: ExpertMLPs,
@@ -342,6 +362,17 @@ class MoE(nn.Module):
         self.dropout = nn.Dropout(moe_dropout) if moe_dropout else None
         self.ep = ps.get_expert_model_parallel_world_size()
 
+    def _fused_path(self, x: torch.Tensor, k: int, E: int) -> bool:
+        from ..ops import moe_fused
+        from ..ops.moe_dispatch import MAX_EXPERTS, MAX_TOP_K
+
+        return bool(
+            moe_fused()   # raises on an invalid NXDT_MOE_FUSED, taken or not
+            and self.ep == 1
+            and E <= MAX_EXPERTS and k <= MAX_TOP_K
+            and self.experts.grouped_chosen(x, x.size(0) * k)
+        )
+
     def forward(self, x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """x: [T, H] (caller flattens [s,b,h]). Returns (y [T, H],
         router_logits [T, E] — computed on the shuffled token order when
@@ -353,6 +384,19 @@ class MoE(nn.Module):
         k = self.router.top_k
         E = self.router.num_experts
         topw, topi, logits = self.router(x)
+
+        if self._fused_path(x, k, E):
+            from ..ops.moe_dispatch import fused_moe_experts
+
+            cap = (int(math.ceil(self.capacity_factor * T * k / E))
+                   if self.capacity_factor else 0)
+            y = fused_moe_experts(x, topw, topi, self.experts.gate_up,
+                                  self.experts.down, cap)
+            if self.dropout is not None:
+                y = self.dropout(y)
+            if shuf_ctx is not None:
+                y = token_unshuffle(y, shuf_ctx)
+            return y, logits
 
         # flatten (token, choice) pairs
         flat_exp = topi.reshape(-1)                   # [T*k]

@@ -25,7 +25,11 @@ products (skinny shrink, expand-add fused with the base output, two-stage
 wgrad; bf16, r in 8/16/32/64), and the fused LM-head + cross-entropy (the
 NT MFMA GEMM hidden @ lm_head^T with the softmax statistics, or the logit
 gradient of a row chunk, as its epilogue: the [tokens, vocab] logits are
-never stored; opt-in, model.fused_lm_head_loss).
+never stored; opt-in, model.fused_lm_head_loss), and the MoE token path
+around the grouped GEMMs (moe_dispatch: a deterministic counting-sort plan
+from topi straight into the padded layout, the permute into it, the fp32
+combine out of it and the combine's backward with the routing-weight
+gradient; opt-in, NXDT_MOE_FUSED=1).
 """
 
 from __future__ import annotations
@@ -125,6 +129,18 @@ def gpt_glue() -> bool:
     return env == "1"
 
 
+def moe_fused() -> bool:
+    """NXDT_MOE_FUSED=1 (read per call; unset or empty means 0) makes
+    modules.moe.MoE take the fused token path of ops.moe_dispatch where it
+    applies: bf16 on the GPU, EP = 1, at most 64 experts and top-8, and a
+    token count at which ExpertMLPs would choose the grouped kernel. Anywhere
+    else, and with 0, the layer evaluates the eager code unchanged."""
+    env = os.environ.get("NXDT_MOE_FUSED", "") or "0"
+    if env not in ("0", "1"):
+        raise ValueError(f"NXDT_MOE_FUSED must be '0' or '1', got {env!r}")
+    return env == "1"
+
+
 from .rmsnorm import rmsnorm  # noqa: E402
 from .layernorm import layernorm  # noqa: E402
 from .gelu import geglu, gelu  # noqa: E402
@@ -140,6 +156,7 @@ from .flash_attn import (  # noqa: E402
 from .flash_decode import flash_attn_decode  # noqa: E402
 from .lora import lora_delta_add  # noqa: E402
 from .lm_head_loss import linear_cross_entropy  # noqa: E402
+from .moe_dispatch import fused_moe_experts  # noqa: E402
 
 __all__ = [
     "have_extension",
@@ -156,6 +173,7 @@ __all__ = [
     "flash_attn_decode",
     "lora_delta_add",
     "linear_cross_entropy",
+    "fused_moe_experts",
     "dropout_keep_mask",
     "dropout_keep_scale",
     "mask_to_kv_range",

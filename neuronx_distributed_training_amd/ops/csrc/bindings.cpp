@@ -883,6 +883,135 @@ torch::Tensor moe_wgrad(torch::Tensor dy, torch::Tensor x,
   return dw;
 }
 
+// ---- MoE token path (moe_dispatch.hip) ----
+// The kernels index dense arrays by values read from the plan tensors; their
+// types, sizes and devices are settled here, their values range-checked in
+// the kernels.
+static MoePlan moe_plan_view(const torch::Tensor& ref, const char* op, long E,
+                             const torch::Tensor& row_src,
+                             const torch::Tensor& tile_expert,
+                             const torch::Tensor& pad_off,
+                             const torch::Tensor& counts,
+                             const torch::Tensor& total) {
+  const long Tp = row_src.numel();
+  TORCH_CHECK(Tp % 256 == 0, op, ": row_src must have a multiple of 256 rows");
+  check_vec(row_src, ref, torch::kInt, Tp, op, "row_src");
+  check_vec(tile_expert, ref, torch::kInt, Tp / 256, op, "tile_expert");
+  check_vec(pad_off, ref, torch::kInt, E + 1, op, "pad_off");
+  check_vec(counts, ref, torch::kLong, E, op, "counts");
+  check_vec(total, ref, torch::kInt, 1, op, "total");
+  return MoePlan{row_src.data_ptr<int>(), tile_expert.data_ptr<int>(),
+                 pad_off.data_ptr<int>(), total.data_ptr<int>(),
+                 (const long*)counts.data_ptr<int64_t>()};
+}
+
+static void check_moe_rows(const torch::Tensor& t, const torch::Tensor& ref,
+                           long rows, long H, const char* op,
+                           const char* name) {
+  check_dense(t, ref, torch::kBFloat16, op, name);
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && (H < 0 || t.size(1) == H),
+              op, ": ", name, " must be [", rows, ", H]");
+  TORCH_CHECK(t.size(1) > 0 && t.size(1) % 8 == 0 && t.size(1) < (1L << 24),
+              op, ": H must be a positive multiple of 8");
+}
+
+static void check_moe_pairs(long T, long topk, const char* op) {
+  TORCH_CHECK(topk >= 1 && topk <= MOE_MAX_TOPK, op, ": top-k must be 1..",
+              MOE_MAX_TOPK, ", got ", topk);
+  TORCH_CHECK(T * topk <= (1L << 30), op, ": too many (token, choice) pairs");
+}
+
+// weights [T, topk], bf16 or fp32; returns whether fp32
+static bool check_moe_w(const torch::Tensor& w, const torch::Tensor& ref,
+                        long T, long topk, const char* op) {
+  const bool f32 = w.scalar_type() == torch::kFloat32;
+  check_dense(w, ref, f32 ? torch::kFloat32 : torch::kBFloat16, op, "w");
+  TORCH_CHECK(w.dim() == 2 && w.size(0) == T && w.size(1) == topk, op,
+              ": w must be [T, top-k]");
+  return f32;
+}
+
+std::vector<torch::Tensor> moe_plan(torch::Tensor topi, long E, long cap) {
+  check_dense(topi, topi, torch::kLong, "moe_plan", "topi");
+  TORCH_CHECK(topi.dim() == 2, "moe_plan: topi must be [T, top-k]");
+  TORCH_CHECK(E >= 1 && E <= MOE_PLAN_MAX_E, "moe_plan: experts must be 1..",
+              MOE_PLAN_MAX_E, ", got ", E);
+  check_moe_pairs(topi.size(0), topi.size(1), "moe_plan");
+  TORCH_CHECK(cap >= 0 && cap < (1L << 31), "moe_plan: capacity out of range");
+  const long P = topi.numel();
+  const long Tp = moe_padded_rows(P, (int)E);
+  auto i32 = topi.options().dtype(torch::kInt);
+  auto table = torch::empty({std::max(moe_plan_chunks(P), 1), E}, i32);
+  auto counts = torch::empty({E}, topi.options());
+  auto pad_off = torch::empty({E + 1}, i32);
+  auto total = torch::empty({1}, i32);
+  auto tile_expert = torch::empty({Tp / 256}, i32);
+  auto slot = torch::empty({P}, i32);
+  auto row_src = torch::empty({Tp}, i32);
+  launch_moe_plan(topi.data_ptr(), table.data_ptr(), counts.data_ptr(),
+                  pad_off.data_ptr(), total.data_ptr(), tile_expert.data_ptr(),
+                  slot.data_ptr(), row_src.data_ptr(), (int)P, (int)E,
+                  (int)cap, Tp, cur_stream());
+  return {counts, pad_off, total, tile_expert, slot, row_src};
+}
+
+torch::Tensor moe_permute(torch::Tensor x, long topk, torch::Tensor row_src,
+                          torch::Tensor tile_expert, torch::Tensor pad_off,
+                          torch::Tensor counts, torch::Tensor total) {
+  check_moe_rows(x, x, x.dim() == 2 ? x.size(0) : -1, -1, "moe_permute", "x");
+  const long T = x.size(0), H = x.size(1);
+  check_moe_pairs(T, topk, "moe_permute");
+  const MoePlan plan = moe_plan_view(x, "moe_permute", counts.numel(), row_src,
+                                     tile_expert, pad_off, counts, total);
+  const long Tp = row_src.numel();
+  auto x_pad = torch::empty({Tp, H}, x.options());
+  launch_moe_permute(x.data_ptr(), x_pad.data_ptr(), plan, (int)T, (int)topk,
+                     (int)H, Tp, cur_stream());
+  return x_pad;
+}
+
+torch::Tensor moe_combine(torch::Tensor y_pad, torch::Tensor slot,
+                          c10::optional<torch::Tensor> w) {
+  check_dense(slot, y_pad, torch::kInt, "moe_combine", "slot");
+  TORCH_CHECK(slot.dim() == 2, "moe_combine: slot must be [T, top-k]");
+  const long T = slot.size(0), topk = slot.size(1);
+  check_moe_pairs(T, topk, "moe_combine");
+  check_moe_rows(y_pad, y_pad, y_pad.dim() == 2 ? y_pad.size(0) : -1, -1,
+                 "moe_combine", "y_pad");
+  const long Tp = y_pad.size(0), H = y_pad.size(1);
+  TORCH_CHECK(Tp < (1L << 31), "moe_combine: too many padded rows");
+  const bool f32 = w && check_moe_w(*w, y_pad, T, topk, "moe_combine");
+  auto y = torch::empty({T, H}, y_pad.options());
+  launch_moe_combine(y_pad.data_ptr(), slot.data_ptr(),
+                     w ? w->data_ptr() : nullptr, f32, y.data_ptr(), (int)T,
+                     (int)topk, (int)H, Tp, cur_stream());
+  return y;
+}
+
+std::vector<torch::Tensor> moe_combine_bwd(
+    torch::Tensor dy, torch::Tensor y_pad, torch::Tensor w, torch::Tensor slot,
+    torch::Tensor row_src, torch::Tensor tile_expert, torch::Tensor pad_off,
+    torch::Tensor counts, torch::Tensor total) {
+  const char* op = "moe_combine_bwd";
+  check_dense(slot, dy, torch::kInt, op, "slot");
+  TORCH_CHECK(slot.dim() == 2, op, ": slot must be [T, top-k]");
+  const long T = slot.size(0), topk = slot.size(1);
+  check_moe_pairs(T, topk, op);
+  check_moe_rows(dy, dy, T, -1, op, "dy");
+  const long H = dy.size(1);
+  const MoePlan plan = moe_plan_view(dy, op, counts.numel(), row_src,
+                                     tile_expert, pad_off, counts, total);
+  const long Tp = row_src.numel();
+  check_moe_rows(y_pad, dy, Tp, H, op, "y_pad");
+  const bool f32 = check_moe_w(w, dy, T, topk, op);
+  auto dy_pad = torch::empty({Tp, H}, dy.options());
+  auto dw = torch::empty_like(w);
+  launch_moe_combine_bwd(dy.data_ptr(), y_pad.data_ptr(), w.data_ptr(), f32,
+                         slot.data_ptr(), dy_pad.data_ptr(), dw.data_ptr(),
+                         plan, (int)T, (int)topk, (int)H, Tp, cur_stream());
+  return {dy_pad, dw};
+}
+
 // ---- LoRA adapter products (lora.hip) ----
 // The kernels index dense row-major bf16 with 16-byte row vectors and have
 // one instantiation per rank, so rank, dtype and alignment are settled here.
@@ -1329,6 +1458,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_bwd", &ce_bwd);
   m.def("moe_gemm", &moe_gemm);
   m.def("moe_wgrad", &moe_wgrad);
+  m.def("moe_plan", &moe_plan, py::arg("topi"), py::arg("experts"),
+        py::arg("capacity") = 0);
+  m.def("moe_permute", &moe_permute, py::arg("x"), py::arg("topk"),
+        py::arg("row_src"), py::arg("tile_expert"), py::arg("pad_off"),
+        py::arg("counts"), py::arg("total"));
+  m.def("moe_combine", &moe_combine, py::arg("y_pad"), py::arg("slot"),
+        py::arg("w") = py::none());
+  m.def("moe_combine_bwd", &moe_combine_bwd, py::arg("dy"), py::arg("y_pad"),
+        py::arg("w"), py::arg("slot"), py::arg("row_src"),
+        py::arg("tile_expert"), py::arg("pad_off"), py::arg("counts"),
+        py::arg("total"));
   m.def("lora_shrink", &lora_shrink, py::arg("x"), py::arg("m"),
         py::arg("scale") = 1.0);
   m.def("lora_expand", &lora_expand, py::arg("h"), py::arg("m"),

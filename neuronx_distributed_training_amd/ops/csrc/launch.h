@@ -143,7 +143,57 @@ static_assert(layernorm_bwd_grid(3, 1032, 256) == 1 &&
                   layernorm_bwd_grid(9, 4096, 256) == 9,
               "rows bound the grid before the CUs do");
 
+// ---- MoE token path (moe_dispatch.hip) ----
+
+// Consecutive (token, choice) pairs per block of the plan's histogram and
+// placement kernels; most experts (one wave lane each) and choices per token.
+constexpr int MOE_PLAN_CHUNK = 1024, MOE_PLAN_MAX_E = 64, MOE_MAX_TOPK = 8;
+constexpr int moe_plan_chunks(long P) {
+  return (int)((P + MOE_PLAN_CHUNK - 1) / MOE_PLAN_CHUNK);
+}
+// Rows of the padded layout for P pairs over E experts, from host values
+// only: every segment rounded up to 256 rows (ops/moe_gemm.py _layout).
+constexpr long moe_padded_rows(long P, int E) {
+  return (P + E * 255L + 255) / 256 * 256;
+}
+static_assert(moe_plan_chunks(0) == 0 && moe_plan_chunks(1025) == 2 &&
+                  moe_padded_rows(600, 4) == 1792 && moe_padded_rows(0, 1) == 256,
+              "a ragged last chunk counts; _layout's Tp_max");
+// Adjacent lanes that hold one row of H bf16 in the permute / combine
+// kernels (256 / lanes rows per block).
+constexpr int moe_row_lanes(int H) { return H <= 512 ? 16 : H <= 2048 ? 64 : 256; }
+static_assert(moe_row_lanes(128) == 16 && moe_row_lanes(640) == 64 &&
+                  moe_row_lanes(4096) == 256,
+              "one 16-byte vector a lane at H = 128; a block a row from 2176");
+// The plan's tensors as the row kernels read them. Padded row r is valid when
+// r < total[0] and r - pad_off[e] < counts[e] with e = tile_expert[r / 256];
+// row_src[r] is then its pair index.
+struct MoePlan {
+  const int *row_src, *tile_expert, *pad_off, *total;
+  const long* counts;
+};
+
 extern "C" {
+// moe_dispatch.hip. plan: topi int64 [P] -> counts int64 [E], pad_off int32
+// [E + 1], total int32 [1], tile_expert int32 [Tp / 256], slot int32 [P] (-1:
+// dropped), row_src int32 [Tp] (valid rows only); table is int32 scratch
+// [moe_plan_chunks(P), E]; cap 0 = dropless; Tp = moe_padded_rows(P, E).
+// permute: x [T, H] bf16 -> x_pad [Tp, H]. combine: y_pad [Tp, H], slot
+// [T, topk], w [T, topk] bf16 or fp32 (w_f32), null = unit weights -> y
+// [T, H]. combine_bwd: dy [T, H], y_pad -> dy_pad [Tp, H], dw [T, topk] in
+// w's type. H % 8 == 0; rows at or past total are never written.
+void launch_moe_plan(const void* topi, void* table, void* counts, void* pad_off,
+                     void* total, void* tile_expert, void* slot, void* row_src,
+                     int P, int E, int cap, long Tp, hipStream_t stream);
+void launch_moe_permute(const void* x, void* x_pad, const MoePlan& plan, int T,
+                        int topk, int H, long Tp, hipStream_t stream);
+void launch_moe_combine(const void* y_pad, const void* slot, const void* w,
+                        bool w_f32, void* y, int T, int topk, int H, long Tp,
+                        hipStream_t stream);
+void launch_moe_combine_bwd(const void* dy, const void* y_pad, const void* w,
+                            bool w_f32, const void* slot, void* dy_pad,
+                            void* dw, const MoePlan& plan, int T, int topk,
+                            int H, long Tp, hipStream_t stream);
 // lm_head_loss.hip: hidden [N, H] and weight [V, H] dense bf16, H % LMHEAD_BK
 // == 0, V % 8 == 0; targets int64 global ids; the shard owns ids
 // [vocab_start, vocab_start + V). fwd: part[N, lmhead_vtiles(V)] float2 (max,

@@ -82,6 +82,48 @@ class _GroupedExpertMLP(torch.autograd.Function):
                 d_down.to(down.dtype))
 
 
+class _PaddedExpertMLP(torch.autograd.Function):
+    """_GroupedExpertMLP on operands already in the padded layout: no
+    _layout, no scatter in and no gather out, in either direction."""
+
+    @staticmethod
+    def forward(ctx, x_pad, tile_e, pad_off, total, gate_up, down):
+        k = kernels_for(x_pad)
+        h_pad = k.moe_gemm(x_pad, gate_up, tile_e, total, False)  # [Tp, 2I]
+        g_pad = k.swiglu_fwd(h_pad)                               # [Tp, I]
+        ctx.save_for_backward(x_pad, h_pad, g_pad, tile_e, pad_off, total,
+                              gate_up, down)
+        return k.moe_gemm(g_pad, down, tile_e, total, False)      # [Tp, H]
+
+    @staticmethod
+    def backward(ctx, dy_pad):
+        (x_pad, h_pad, g_pad, tile_e, pad_off, total,
+         gate_up, down) = ctx.saved_tensors
+        k = kernels_for(dy_pad)
+        E = gate_up.size(0)
+        dy_pad = dy_pad.contiguous()
+        d_down = k.moe_wgrad(dy_pad, g_pad, pad_off, E)        # [E, H, I]
+        dg_pad = k.moe_gemm(dy_pad, down, tile_e, total, True)  # [Tp, I]
+        dh_pad = k.swiglu_bwd(dg_pad, h_pad)                    # [Tp, 2I]
+        d_gu = k.moe_wgrad(dh_pad, x_pad, pad_off, E)          # [E, 2I, H]
+        dx_pad = k.moe_gemm(dh_pad, gate_up, tile_e, total, True)  # [Tp, H]
+        return (dx_pad, None, None, None, d_gu.to(gate_up.dtype),
+                d_down.to(down.dtype))
+
+
+def padded_expert_mlp(x_pad: torch.Tensor, tile_expert: torch.Tensor,
+                      pad_off: torch.Tensor, total: torch.Tensor,
+                      gate_up: torch.Tensor, down: torch.Tensor):
+    """x_pad: [Tp, H] tokens in the padded layout (each expert's segment
+    256-row aligned, its padding rows zero; rows at or past `total` are
+    ignored), with tile_expert / pad_off / total as `_layout` returns them.
+    Returns y_pad [Tp, H] in the same layout. The incoming gradient must be
+    zero in the padding rows of every segment, as ops.moe_dispatch's combine
+    writes it: the weight gradients contract whole segments."""
+    return _PaddedExpertMLP.apply(x_pad, tile_expert, pad_off, total,
+                                  gate_up, down)
+
+
 def grouped_expert_mlp(x: torch.Tensor, counts: torch.Tensor,
                        gate_up: torch.Tensor, down: torch.Tensor):
     """x: [T, H] expert-sorted tokens; counts: [E_local] device int64;

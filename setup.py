@@ -38,6 +38,7 @@ sources = [
         "attn_dropout.hip",
         "cross_entropy.hip",
         "moe_gemm.hip",
+        "moe_dispatch.hip",
         "lora.hip",
         "lm_head_loss.hip",
         "probe.hip",

@@ -14,6 +14,54 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 
+def fused_arm(args):
+    """Eager and fused token path alternated in one process: after a warm-up
+    of both, `--windows` device-synchronised windows of `--iters` layer
+    steps per arm; medians."""
+    import statistics
+
+    from neuronx_distributed_training_amd.parallel import state as ps
+    from neuronx_distributed_training_amd.modules.moe import (
+        ExpertMLPs, MoE, RouterTopK)
+
+    ps.initialize_model_parallel()
+    E, H, I, T = args.experts, args.hidden, args.inter, args.tokens
+    bf = torch.bfloat16
+    moe = MoE(RouterTopK(H, E, 2, dtype=bf, init_seed=3).cuda(),
+              ExpertMLPs(E, H, I, dtype=bf, init_seed=1).cuda())
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(T, H, generator=g).to(bf).cuda().requires_grad_(True)
+    dout = torch.randn(T, H, generator=g).to(bf).cuda()
+
+    def step(fused):
+        os.environ["NXDT_MOE_FUSED"] = fused
+        y, _ = moe(x)
+        y.backward(dout)
+        x.grad = None
+        moe.zero_grad(set_to_none=True)
+
+    def window(fused):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.iters):
+            step(fused)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.iters * 1000
+
+    for _ in range(3):
+        step("0")
+        step("1")
+    times = {"0": [], "1": []}
+    for _ in range(args.windows):
+        for arm in ("0", "1"):
+            times[arm].append(window(arm))
+    eager, fused = (statistics.median(times[a]) for a in ("0", "1"))
+    print(f"MoE layer T={T} E={E} top-2 (~{2 * T // E} rows/expert) fwd+bwd: "
+          f"eager {eager:.3f} ms [{min(times['0']):.3f}..{max(times['0']):.3f}]"
+          f"  fused {fused:.3f} ms [{min(times['1']):.3f}.."
+          f"{max(times['1']):.3f}]  eager/fused {eager / fused:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=8192)
@@ -21,7 +69,15 @@ def main():
     ap.add_argument("--experts", type=int, default=8)
     ap.add_argument("--hidden", type=int, default=4096)
     ap.add_argument("--inter", type=int, default=14336)
+    ap.add_argument("--fused", action="store_true",
+                    help="time the whole MoE layer (router to output, fwd + "
+                         "bwd) with NXDT_MOE_FUSED=1 against the eager token "
+                         "path; --tokens is then the layer's T (top-2: "
+                         "2 * T / experts rows per expert)")
+    ap.add_argument("--windows", type=int, default=7)
     args = ap.parse_args()
+    if args.fused:
+        return fused_arm(args)
 
     from neuronx_distributed_training_amd.parallel import state as ps
     from neuronx_distributed_training_amd.modules.moe import ExpertMLPs
